@@ -15,23 +15,31 @@ advance (obs -> a fresh buffer, the form the device rollout buffer uses) is time
 as well and reported under "alt". `step_path` names the kernels one step launches.
 
 Legs, in order (one process per GPU):
-  1. parity leg, every rank: 64 steps of the bench's own workload through the same
-     handle and buffers that are then timed; the first S envs' rewards and values
-     are kept and, after the timed region, checked against the CPU restatement on
-     the same inputs. It also carries the GPU past its start-up clock transient
-     (profiles/warm_curve_r02a.json: steps 3-25 of a cold process run up to 1.3x
-     slower), so the timed steps start at steady state whatever --warmup is.
+  1. lead-in, every rank: 64 steps of the bench's own workload through the same
+     handle and buffers that are then timed. It carries the GPU past its start-up
+     clock transient (profiles/warm_curve_r02a.json: steps 3-25 of a cold process
+     run up to 1.3x slower), so the timed steps start at steady state whatever
+     --warmup is. With --full it is also the parity leg: the first S envs' rewards
+     and values are kept and, after the timed region, checked against the CPU
+     restatement on the same inputs.
   2. --warmup untimed steps, then exactly --steps timed steps between barriers and
      device synchronisations; max over ranks.
-  3. the other window mode (alt), the collective (N > 1), then on rank 0 at N = 1
-     the CPU baseline and the replay of the reference's own recorded outputs.
+  3. --dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy.
+  4. --full only: the other window mode (alt), the collective (N > 1), the parity
+     check, then on rank 0 at N = 1 the CPU baseline and the replay of the
+     reference's own recorded outputs.
+
+A plain run (no --full) stops after leg 3 and prints the result line with the keys
+of legs 4 set to null; the headline (value, ms_per_step, roofline) is the same
+measurement either way.
 
 Multi-GPU runs are strong-scaled by default: the north star's 65,536 envs in total,
 sharded over the ranks by global id (BASELINE config 4: 8,192 per GPU at N = 8; no
 collective in the step); --global-envs G sets the total, --weak keeps 65,536 envs per
 rank instead:
 
-    python bench.py                                   # N = 1
+    python bench.py                                   # N = 1, the headline alone
+    python bench.py --full                            # + alt, parity, CPU baseline, reference replay
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -68,6 +76,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: the other window mode (--alt-steps), "
+                         "the parity check against the CPU restatement (--parity-envs), the CPU baseline "
+                         "(--cpu-baseline), the replay of the reference's recorded outputs, the non-finite count, "
+                         "and at N > 1 the collective and --alt-weak-steps; off: their keys are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step handed its caller as DIR/<name>.npy: reward (f32, every "
+                         "env), value (f64, every env) and obs (f32, the latest window of a fixed seeded sample "
+                         "of envs, listed in obs_envs); ranks above 0 write <name>_rank<r>.npy")
     ap.add_argument("--global-envs", type=int, default=None,
                     help="strong scaling (the default): this many envs in total, sharded over the ranks "
                          "(north star / BASELINE config 4: 65,536 over 1/2/4/8 GPUs); default 65536")
@@ -101,6 +118,10 @@ def parse():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI; gloo lets several ranks share one GPU (functional rehearsal)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:                                # the other legs' own options are read under --full only
+        args.alt_steps = args.alt_weak_steps = args.cpu_baseline = 0
     if args.envs_per_gpu is not None or args.weak:
         if args.global_envs is not None:
             ap.error("--global-envs (strong scaling) and --envs-per-gpu / --weak (weak scaling) exclude each other")
@@ -298,6 +319,34 @@ def sha256_file(path):
     return h.hexdigest()
 
 
+DUMP_BYTES = 40 * 10**6   # --dump-outputs: budget of the sampled window
+DUMP_TOTAL = 60 * 10**6   # ... and of the whole dump
+
+
+def dump_outputs(args, rank, reward, value, window):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy — the
+    reward (f32 [B]) and the portfolio value (f64 [B]) of every env, and the latest window
+    (f32 [n, N, W, F]) of a fixed sample of envs drawn from --seed (every env when they fit
+    DUMP_BYTES); obs_envs lists the sampled env ids (f64). Past a million envs the reward and
+    the value are the sample's as well. The inputs are a function of the arguments alone, so
+    two builds run with the same arguments are compared file by file."""
+    import numpy as np
+    import torch
+    B = reward.shape[0]
+    n = max(1, min(B, DUMP_BYTES // (window[0].numel() * 4)))
+    ids = np.sort(np.random.default_rng(args.seed).choice(B, size=n, replace=False)) if n < B else np.arange(B)
+    sel = torch.as_tensor(ids, device=window.device)
+    out = {"reward": reward, "value": value, "obs": window.index_select(0, sel), "obs_envs": ids}
+    if B * 12 > DUMP_TOTAL - DUMP_BYTES - ids.size * 8:
+        out["reward"], out["value"] = reward.index_select(0, sel), value.index_select(0, sel)
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    for name, a in out.items():
+        a = a.cpu().numpy() if isinstance(a, torch.Tensor) else a
+        np.save(os.path.join(args.dump_outputs, f"{name}{sfx}.npy"),
+                np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64))
+
+
 def spread(us):
     """min / median / max of the sampled kernel times, and which sample was the slowest
     (sample i brackets timed step EVENT_EVERY * i, or 4 EVENT_EVERY * i for cache-resident windows)."""
@@ -396,17 +445,22 @@ def main():
         if rc != 0:
             _abi.check(rc, h, "pmenv_step_ex")
 
-    # ---- 1. parity leg on the timed handle (every rank). Its records stay on the GPU
-    # until after the timed region: no host copy (and no idle GPU) between this leg and
-    # the timed steps, so the clocks it brought up are still up when the timing starts.
+    # ---- 1. lead-in on the timed handle (every rank): the steps that bring the clocks up.
+    # Under --full they are the parity leg as well; its records stay on the GPU until after
+    # the timed region: no host copy (and no idle GPU) between this leg and the timed
+    # steps, so the clocks it brought up are still up when the timing starts.
     S = min(args.parity_envs if world == 1 else 256, B)
-    rec_obs0 = obs[:S].clone()
+    if args.full:
+        rec_obs0 = obs[:S].clone()
     env.reset(obs)
-    rec_r = torch.empty(PARITY_STEPS, S, dtype=torch.float32, device=dev)
+    if args.full:
+        rec_r = torch.empty(PARITY_STEPS, S, dtype=torch.float32, device=dev)
     for i in range(PARITY_STEPS):
         one_step(i, False)
-        rec_r[i].copy_(reward[:S])
-    rec_v, rec_obs = env.value[:S].clone(), obs[:S].clone()
+        if args.full:
+            rec_r[i].copy_(reward[:S])
+    if args.full:
+        rec_v, rec_obs = env.value[:S].clone(), obs[:S].clone()
     # back to the initial window and a fresh env state for the timed legs
     obs.copy_(synth.window_from_series(series, W, F))
     env.reset(obs)
@@ -441,6 +495,10 @@ def main():
     elapsed, k_us = timed(args.steps, args.warmup, double)
     ev_every = timed.every
     kern_avg_s = sum(k_us) / len(k_us) / 1e6
+    if args.dump_outputs:
+        # the last timed step's window: in place it is obs; double-buffered, the side it wrote
+        last = args.warmup + args.steps - 1
+        dump_outputs(args, rank, reward, env.value, obs_b if double and last % 2 == 0 else obs)
     alt = None
     if args.alt_steps > 0:
         # the other window mode, continuing from the latest window
@@ -458,6 +516,7 @@ def main():
                          device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, kern_avg_s = float(t[0]), float(t[1])
+    if world > 1 and args.full:
         # the path's one exchange (outside the timed step loop): the advantage-
         # normalisation moments of the last rewards, {count, sum, sum of squares} f64
         # from the HIP moments kernel, summed over ranks (pmenv.parallel.normalize)
@@ -478,24 +537,26 @@ def main():
     alt_weak = None
     if world > 1 and not args.weak and args.alt_weak_steps > 0:
         alt_weak = weak_leg(args, rank, world, dev, lib, _abi, synth, TradingEnv, torch, dist)
-    nonfinite = env.nonfinite_count()
 
-    # ---- 3. checks and baselines (after the timed region)
-    idx = [t % H for t in range(PARITY_STEPS)]      # the leg cycles through the H resident days
-    rec = (rec_obs0.cpu().numpy(), series[W:W + H, :S].cpu().numpy()[idx], actions[:, :S].cpu().numpy()[idx],
-           rec_r.cpu().numpy(), rec_v.cpu().numpy(), rec_obs.cpu().numpy())
-    del rec_obs0, rec_obs
-    parity = parity_check(args, rec, lo, torch)
-    if world > 1:
-        t = torch.tensor([parity["reward_max_rel"], parity["value_max_rel"], 0.0 if parity["obs_bit_exact"] else 1.0],
-                         dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        parity.update({"reward_max_rel_all_ranks": float(t[0]), "value_max_rel_all_ranks": float(t[1]),
-                       "obs_bit_exact_all_ranks": float(t[2]) == 0.0})
-    cpu = ref_gold = None
-    if rank == 0 and world == 1 and args.cpu_baseline:
-        cpu = cpu_baseline(args, series, actions, H, torch)
-        ref_gold = reference_golden_mae(dev, torch, TradingEnv)
+    # ---- 4. checks and baselines (--full, after the timed region)
+    nonfinite = parity = cpu = ref_gold = None
+    if args.full:
+        nonfinite = env.nonfinite_count()
+        idx = [t % H for t in range(PARITY_STEPS)]      # the leg cycles through the H resident days
+        rec = (rec_obs0.cpu().numpy(), series[W:W + H, :S].cpu().numpy()[idx],
+               actions[:, :S].cpu().numpy()[idx], rec_r.cpu().numpy(), rec_v.cpu().numpy(), rec_obs.cpu().numpy())
+        del rec_obs0, rec_obs
+        parity = parity_check(args, rec, lo, torch)
+        if world > 1:
+            t = torch.tensor([parity["reward_max_rel"], parity["value_max_rel"],
+                              0.0 if parity["obs_bit_exact"] else 1.0],
+                             dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            parity.update({"reward_max_rel_all_ranks": float(t[0]), "value_max_rel_all_ranks": float(t[1]),
+                           "obs_bit_exact_all_ranks": float(t[2]) == 0.0})
+        if rank == 0 and world == 1 and args.cpu_baseline:
+            cpu = cpu_baseline(args, series, actions, H, torch)
+            ref_gold = reference_golden_mae(dev, torch, TradingEnv)
 
     kernel = paths[0 if double else -1].split(" (")[0].split("+")[-1]
     total_env_steps = (world * B if args.weak else args.global_envs) * args.steps
@@ -578,7 +639,8 @@ def main():
                          if l3 else "window streams through HBM (larger than the 256 MiB Infinity Cache)"),
             },
             "cpu_baseline": cpu,
-            "reward_mae": parity["reward_mae"],
+            "full": args.full,
+            "reward_mae": parity and parity["reward_mae"],
             "parity_sample": parity,
             "reference_goldens": ref_gold,
             "nonfinite_envs": nonfinite,

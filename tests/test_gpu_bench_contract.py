@@ -1,7 +1,7 @@
 """bench.py's output contract, on a small workload: one JSON line on stdout with the
-driver's keys, the roofline and cpu_baseline objects, a parity record against the CPU
-restatement, and no PMENV_* knob. Runs bench.py as a child process (fresh GPU context).
-Needs an MI355X."""
+driver's keys and the roofline object; with --full the cpu_baseline object and a parity
+record against the CPU restatement; --dump-outputs; and no PMENV_* knob. Runs bench.py as
+a child process (fresh GPU context). Needs an MI355X."""
 import json
 import os
 import subprocess
@@ -13,9 +13,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(*extra, env=None):
+def _run(*extra, env=None, full=True):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--envs-per-gpu", "2048", "--steps", "8", "--warmup", "2",
-           "--alt-steps", "4", "--cpu-sample-envs", "256", "--cpu-budget-s", "0.5", "--parity-envs", "256", *extra]
+           "--alt-steps", "4", "--cpu-sample-envs", "256", "--cpu-budget-s", "0.5", "--parity-envs", "256",
+           *(["--full"] if full else []), *extra]
     return subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env)
 
 
@@ -52,6 +53,57 @@ def test_bench_prints_the_contract_line():
     assert d["reward_mae"] <= 1e-6
 
 
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full the line keeps the headline keys and leaves every other leg's key
+    null; --dump-outputs writes what the last timed step returned (reward f32, value f64,
+    the latest window f32), the same from run to run, and equal to the CPU restatement
+    stepped over the same 10 days (smoke()'s tolerances)."""
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    outs = []
+    for name in ("a", "b"):
+        p = _run("--dump-outputs", str(tmp_path / name), full=False)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, p.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["full"] is False and d["steps"] == 8 and d["warmup"] == 2 and d["higher_is_better"] is True
+        assert d["unit"] == "env-steps/s" and d["dtype"] == "f64" and d["metric"].startswith("env-steps/sec")
+        assert d["value"] > 0 and abs(d["value"] - 2048 * 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
+        assert d["roofline"]["achieved"] > 0 and d["library"]["sha256"]
+        for k in ("cpu_baseline", "alt", "reward_mae", "parity_sample", "reference_goldens", "nonfinite_envs"):
+            assert d[k] is None, k
+        files = sorted(f.name for f in (tmp_path / name).iterdir())
+        assert files == ["obs.npy", "obs_envs.npy", "reward.npy", "value.npy"]
+        outs.append({f[:-4]: np.load(tmp_path / name / f) for f in files})
+    a, b = outs
+    assert a["reward"].dtype == np.float32 and a["value"].dtype == np.float64 and a["obs"].dtype == np.float32
+    assert a["reward"].shape == (2048,) and a["value"].shape == (2048,) and a["obs"].shape == (1333, 30, 50, 5)
+    assert sum(v.nbytes for v in a.values()) <= 64e6
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+    from oracle import OracleEnv
+    from pmenv import synth
+    from pmenv.config import EnvConfig
+    B, N, W, F, T = 2048, 30, 50, 5, 10                  # bench.py's defaults; T = warmup + steps
+    ser = synth.series(64 + W, B, N, seed=42, device="cuda:0")
+    act = synth.actions(64, B, N, seed=43, device="cuda:0").cpu().numpy()
+    cobs = synth.window_from_series(ser, W, F).cpu().numpy().copy()
+    ser = ser.cpu().numpy()
+    cenv = OracleEnv(EnvConfig(num_envs=B, num_assets=N, window=W, features=F))
+    cenv.reset(cobs)
+    for t in range(T):
+        cr, _, _ = cenv.step(act[t], cobs, bar=ser[W + t])
+    ids = a["obs_envs"].astype(np.int64)
+    assert np.all(np.abs(a["reward"].astype(np.float64) - cr) <= 1e-6 * np.abs(cr) + 1e-9)
+    assert np.allclose(a["value"], cenv.value, rtol=1e-12, atol=0)
+    assert np.array_equal(a["obs"][..., :4], cobs[ids][..., :4])
+    assert np.allclose(a["obs"][..., 4], cobs[ids][..., 4], rtol=2e-7, atol=1e-12)
+
+
 def test_bench_refuses_a_knob():
     import torch
     if not torch.cuda.is_available():
@@ -68,7 +120,7 @@ def _two_ranks(*extra):
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2",
-           "--dist-backend", "gloo", "--steps", "8", "--warmup", "2", "--alt-steps", "0", *extra]
+           "--dist-backend", "gloo", "--full", "--steps", "8", "--warmup", "2", "--alt-steps", "0", *extra]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]

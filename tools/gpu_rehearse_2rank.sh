@@ -4,13 +4,14 @@
 set -u
 TAG=${1:-r02}
 export TMPDIR=/tmp
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}   # where the records go
+mkdir -p $OUT
 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port 29511 bench.py --gpus 2 --steps 50 --warmup 5 --dist-backend gloo \
-    > gpurun_out/bench_2rank_rehearsal_$TAG.json 2> gpurun_out/bench_2rank_rehearsal_$TAG.err || exit $?
+    --master-port 29511 bench.py --gpus 2 --full --steps 50 --warmup 5 --dist-backend gloo \
+    > $OUT/bench_2rank_rehearsal_$TAG.json 2> $OUT/bench_2rank_rehearsal_$TAG.err || exit $?
 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port 29512 bench.py --gpus 2 --global-envs 65536 --steps 50 --warmup 5 --dist-backend gloo \
-    > gpurun_out/bench_2rank_strong_$TAG.json 2> gpurun_out/bench_2rank_strong_$TAG.err || exit $?
+    --master-port 29512 bench.py --gpus 2 --full --global-envs 65536 --steps 50 --warmup 5 --dist-backend gloo \
+    > $OUT/bench_2rank_strong_$TAG.json 2> $OUT/bench_2rank_strong_$TAG.err || exit $?
 for i in 1 2; do
-  timeout -k 10 300 python bench.py --cpu-baseline 0 > gpurun_out/bench_rep${i}_$TAG.json 2> gpurun_out/bench_rep${i}_$TAG.err || exit $?
+  timeout -k 10 300 python bench.py --full --cpu-baseline 0 > $OUT/bench_rep${i}_$TAG.json 2> $OUT/bench_rep${i}_$TAG.err || exit $?
 done

@@ -5,13 +5,14 @@
 set -u
 TAG=${1:-r04}
 export TMPDIR=/tmp
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}   # where the records go
+mkdir -p $OUT
 for S in 32768 16384 8192; do
-  timeout -k 10 300 python bench.py --global-envs $S --cpu-baseline 0 \
-      > gpurun_out/share_${S}_$TAG.json 2> gpurun_out/share_${S}_$TAG.err || exit $?
-  tail -1 gpurun_out/share_${S}_$TAG.json | cut -c1-200
+  timeout -k 10 300 python bench.py --full --global-envs $S --cpu-baseline 0 \
+      > $OUT/share_${S}_$TAG.json 2> $OUT/share_${S}_$TAG.err || exit $?
+  tail -1 $OUT/share_${S}_$TAG.json | cut -c1-200
 done
 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port 29513 bench.py --gpus 2 --steps 50 --warmup 5 --dist-backend gloo \
-    > gpurun_out/bench_2rank_strong_$TAG.json 2> gpurun_out/bench_2rank_strong_$TAG.err || exit $?
-tail -1 gpurun_out/bench_2rank_strong_$TAG.json | cut -c1-300
+    --master-port 29513 bench.py --gpus 2 --full --steps 50 --warmup 5 --dist-backend gloo \
+    > $OUT/bench_2rank_strong_$TAG.json 2> $OUT/bench_2rank_strong_$TAG.err || exit $?
+tail -1 $OUT/bench_2rank_strong_$TAG.json | cut -c1-300
