@@ -36,7 +36,8 @@ extern "C" {
  *    pmenv_cfg_default's ret_mode is PMENV_RET_GROSS (trading_env.py:88 for every reward
  *    kind; was AUTO in 1) */
 /* 3: pmenv_step_host / pmenv_reset_host (host buffers, the reference driver's call shape) */
-#define PMENV_ABI_VERSION 3
+/* 4: pmenv_replay_gather_nstep (n-step return samples of the replay ring) */
+#define PMENV_ABI_VERSION 4
 
 /* Opaque HIP stream (identical to HIP's own typedef); NULL = default stream. */
 typedef struct ihipStream_t* hipStream_t;
@@ -391,6 +392,30 @@ int pmenv_replay_gather(const float* series, int32_t T, int32_t N, int32_t F, in
                         const int32_t* days, const float* actions, const float* rewards,
                         int32_t H, int32_t B, const int32_t* h0, const int32_t* env, int32_t S,
                         float* s, float* s_next, float* a_out, float* r_out, hipStream_t stream);
+
+/* The n-step sample of the same ring: agent/td3/td3.py:85-106 (add_experience) folds the
+ * last n_step transitions into one before it stores them — reward = r + gamma * reward *
+ * (1 - d) from the back (:94-96), the first state and action, the next state of the step
+ * where the fold stopped; here every step is already recorded (replay/buffer.py:39-79),
+ * so the fold happens at sample time. The ring holds `count` <= H recorded rows, the
+ * oldest at row `oldest`; row h has position (h - oldest) mod H. row_episode [H] int32
+ * is each row's episode id, not decreasing from the oldest row to the newest (NULL = one
+ * episode). For a valid one-step sample (h0[j], env[j]) at position st, m is the largest
+ * count in [1, n] such that st + m - 1 < count - W - 1 and rows st .. st + m - 1 + W share
+ * one episode (td3's `done`: an episode boundary or the newest rows end the fold early).
+ * Writes s, a_out as pmenv_replay_gather does; s_next = that call's s_next for the start
+ * h0 + m - 1 (the window ending at days[h0+m+W-2] + 1, channel F-1 = actions h0+m ..
+ * h0+m+W-1); r_out [S] = sum_{k<m} gamma^k rewards[h0+W-1+k], Horner from the last term
+ * in f64, rounded once; steps [S] = m; discount [S] = gamma^m (f64 product). n = 1 is
+ * pmenv_replay_gather bit for bit. PMENV_ERR_ARG: n < 1, count > H, oldest outside
+ * [0, H), gamma outside (0, 1], a NULL pointer other than row_episode. */
+int pmenv_replay_gather_nstep(const float* series, int32_t T, int32_t N, int32_t F, int32_t W,
+                              const int32_t* days, const float* actions, const float* rewards,
+                              int32_t H, int32_t B, const int32_t* h0, const int32_t* env, int32_t S,
+                              const int32_t* row_episode /* [H], NULL = one episode */,
+                              int32_t oldest, int32_t count, int32_t n, float gamma,
+                              float* s, float* s_next, float* a_out, float* r_out,
+                              int32_t* steps, float* discount, hipStream_t stream);
 
 /* The compact on-policy rollout (replay/rollout_buffer.py:43-57 stores s per step;
  * here the windows are re-materialised instead): for each of the S

@@ -1386,6 +1386,71 @@ int pmenv_replay_gather(const float* series, int32_t T, int32_t N, int32_t F, in
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
 
+int pmenv_replay_gather_nstep(const float* series, int32_t T, int32_t N, int32_t F, int32_t W, const int32_t* days,
+                              const float* actions, const float* rewards, int32_t H, int32_t B, const int32_t* h0,
+                              const int32_t* env, int32_t S, const int32_t* row_episode, int32_t oldest,
+                              int32_t count, int32_t n, float gamma, float* s, float* s_next, float* a_out,
+                              float* r_out, int32_t* steps, float* discount, hipStream_t stream) {
+    if (!series || !days || !actions || !rewards || !h0 || !env || !s || !s_next || !a_out || !r_out || !steps ||
+        !discount || T < 1 || N < 1 || F < 2 || W < 1 || H < W + 1 || B < 1 || S < 1 || n < 1 || count < 0 ||
+        count > H || oldest < 0 || oldest >= H || !(gamma > 0.0f && gamma <= 1.0f))
+        return PMENV_ERR_ARG;
+    const NstepRing rg{row_episode, oldest, count, n, (double)gamma};
+    // the staged image holds the union of two overlapping windows: W + min(n, W) days.
+    // Same forms and the same asset-group rule as pmenv_replay_gather with that image:
+    // R divides N, R*W*F is a multiple of 4, at most 12 (day, asset) pairs per thread
+    // (N = 30, W = 50 keeps whole samples up to the disjoint case, 3,000 pairs), the
+    // image within 64 KiB. Measured at config 3's shape (S = 8,192, N = 30, W = 50) beside
+    // the one-step gather's 97 us: 122 us at n = 1, 126 us at n = 5, 245 us at n = 64
+    // (tools/bench_rows.py, profiles/rows_nstep.json). The generic LDS form has the
+    // one-step generic form's structure, which runs 198 us there: slower than the fast
+    // form at n <= 5 already on the one-step figure, and not timed at n = 64.
+    const int D = W + (n < W ? n : W);
+    const size_t lds = (size_t)N * D * F * sizeof(float);
+    const bool al16 = ((uintptr_t)s & 15u) == 0 && ((uintptr_t)s_next & 15u) == 0 && ((uintptr_t)series & 15u) == 0;
+    int R = 0;
+    if (F == 5 && al16) {
+        for (int r = N; r >= 1; --r)
+            if (N % r == 0 && ((int64_t)r * W * F) % 4 == 0 && (int64_t)r * D <= 12 * 256 && r <= 256 &&
+                (size_t)r * D * F * sizeof(float) <= 64 * 1024) {
+                R = r;
+                break;
+            }
+    }
+    if (R > 0) {
+        const FastDiv dr = make_fastdiv((uint32_t)R), dwf = make_fastdiv((uint32_t)(W * F));
+        const size_t glds = (size_t)R * D * F * sizeof(float);
+        const int pairs = R * D;
+        static int cus = 0;                                // one workgroup per CU, as the one-step gather
+        if (!cus) {
+            int dev = 0;
+            if (hipGetDevice(&dev) != hipSuccess ||
+                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+                cus = 256;
+        }
+        const int gy = N / R;
+        const int G = cus / gy > 0 ? cus / gy : 1;
+        const dim3 pgrid((unsigned)(S < G ? S : G), (unsigned)gy);
+        const int ppt = pairs <= 2 * 256 ? 2 : pairs <= 4 * 256 ? 4 : pairs <= 8 * 256 ? 8 : 12;
+#define PMENV_RNP(PPT)                                                                                         \
+    replay_nstep_f5p_kernel<PPT, 2><<<pgrid, 256, glds, stream>>>(series, T, N, W, days, actions, rewards, H, B, \
+                                                                  h0, env, S, rg, D, s, s_next, a_out, r_out,  \
+                                                                  steps, discount, R, dr, dwf)
+        if (ppt == 2) PMENV_RNP(2); else if (ppt == 4) PMENV_RNP(4); else if (ppt == 8) PMENV_RNP(8); else PMENV_RNP(12);
+#undef PMENV_RNP
+    } else if (lds <= 64 * 1024 && N <= 256 && ((uintptr_t)s & 15u) == 0 && ((uintptr_t)s_next & 15u) == 0) {
+        replay_nstep_lds_kernel<<<(unsigned)S, 256, lds, stream>>>(series, T, N, F, W, days, actions, rewards, H, B,
+                                                                  h0, env, rg, D, s, s_next, a_out, r_out, steps,
+                                                                  discount);
+    } else {
+        const int64_t threads = (int64_t)S * N * W * F;
+        replay_nstep_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(
+            series, T, N, F, W, days, actions, rewards, H, B, h0, env, S, rg, s, s_next, a_out, r_out, steps,
+            discount);
+    }
+    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
 int pmenv_rollout_gather(const float* series, int32_t T, int32_t N, int32_t F, int32_t W, const int32_t* start,
                          const float* weights, int32_t T_rec, int32_t B, int32_t ring_mode, const int32_t* t_idx,
                          const int32_t* env, int32_t S, float* s, hipStream_t stream) {

@@ -8,6 +8,8 @@
 //   s' = window ending at day[h0+W-1, b] + 1  with channel F-1 = actions[h0+1 .. h0+W, b]
 //   a  = actions[h0+W, b],  r = rewards[h0+W-1, b]                (buffer.py:59-72)
 // from the resident market series [T, N, F-1]. Recorded steps are a ring of H rows.
+// The replay_nstep_* kernels fold up to n such transitions into one at sample time
+// (agent/td3/td3.py:85-106): see "n-step samples" below.
 //
 // metrics_kernel restates util/eval.py:14-37 per env over a [T, B] trajectory with
 // quantstats' published definitions (quantstats is not installed here: parity unpinned).
@@ -562,6 +564,399 @@ __global__ __launch_bounds__(256) void replay_gather_f5p_kernel(const float* ser
         bc = b1; hc = h1; dc = d1;
         b1 = b2; h1 = h2; d1 = d2; m1 = m2;
         b2 = b3; h2 = h3; m2 = m3;
+    }
+}
+
+// ---------------------------------------------------------------- n-step samples
+// agent/td3/td3.py:85-106 (add_experience) folds the last n_step transitions into one
+// before it stores them: reward = r + gamma * reward * (1 - d) from the back (:94-96),
+// the first state and action, the next state of the step where the fold stopped. Here
+// the ring already holds every step, so the fold happens at sample time: for a valid
+// one-step sample (h0, b), with st = (h0 - oldest) mod H its position in the ring,
+//   m  = the largest count in [1, n] whose one-step starts st .. st+m-1 are all valid:
+//        st+m-1 < count-W-1 and rows st .. st+m-1+W share one episode (td3's `done`:
+//        an episode boundary or the newest recorded rows end the fold early)
+//   s, a = the one-step sample's at h0;  s' = the one-step sample's s' at h0+m-1
+//   R  = sum_{k<m} gamma^k rewards[h0+W-1+k, b], Horner from the last term in f64
+//   steps = m, discount = gamma^m (f64 product)
+// Episode ids do not decrease from the oldest row to the newest, so the rows
+// st .. st+k+W share one episode iff the last one carries the first one's id.
+
+struct NstepRing {
+    const int32_t* row_ep;   // [H] episode id per ring row, nullptr = one episode
+    int oldest, count, n;
+    double gamma;
+};
+
+// the cap nn of m from the recorded rows alone, and the episode ids that decide
+// whether it holds: E of row h, far of the last row of start st+nn-1
+__device__ __forceinline__ int nstep_cap(const NstepRing& rg, int H, int W, int h) {
+    int st = h - rg.oldest;
+    st = st < 0 ? st + H : st;
+    const int nn = min(rg.n, rg.count - W - 1 - st);
+    return nn < 1 ? 1 : nn;
+}
+// ring rows below 2H / 3H back into [0, H) without a division
+__device__ __forceinline__ int ring_wrap(int x, int H) { return x >= H ? x - H : x; }
+__device__ __forceinline__ int nstep_last_row(int H, int W, int h, int k) {   // k <= count - W - 1
+    return ring_wrap(ring_wrap(h + W + k - 1, H), H);
+}
+// m from E, far: nn when the farthest window still lies in the episode (two loads, one
+// round trip), else the boundary by bisection — start st is valid, start st+nn-1 is not
+__device__ __forceinline__ int nstep_finish(const NstepRing& rg, int H, int W, int h, int nn, int E, int far) {
+    if (far == E) return nn;
+    int lo = 1, hi = nn;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (rg.row_ep[nstep_last_row(H, W, h, mid)] == E) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ int nstep_count(const NstepRing& rg, int H, int W, int h) {
+    const int nn = nstep_cap(rg, H, W, h);
+    if (!rg.row_ep || nn == 1) return nn;
+    return nstep_finish(rg, H, W, h, nn, rg.row_ep[h], rg.row_ep[nstep_last_row(H, W, h, nn)]);
+}
+
+// R and gamma^m by one thread: acc = r_k + gamma * acc from the last term (td3.py:94-96)
+__device__ __forceinline__ void nstep_fold_serial(const float* rewards, int H, int B, int b, int hr, int m,
+                                                  double gamma, float* R, float* disc) {
+    double acc = 0.0, g = 1.0;
+    for (int k = m - 1; k >= 0; --k) {
+        acc = (double)rewards[(size_t)((hr + k) % H) * B + b] + gamma * acc;
+        g *= gamma;
+    }
+    *R = (float)acc;
+    *disc = (float)g;
+}
+
+// The same fold by one wave: lane l holds reward k0 + l of a chunk of 64 (`first` is the
+// chunk k0 = 0, loaded with the sample's staging loads), the Horner chain walks the
+// lanes from the back through v_readlane — the m loads are not a dependent chain.
+__device__ __forceinline__ void nstep_fold_wave(const float* rewards, int H, int B, int b, int hr, int m, float first,
+                                                double gamma, float* R, float* disc) {
+    const int lane = threadIdx.x & 63;
+    double acc = 0.0, g = 1.0;
+    for (int k0 = ((m - 1) >> 6) << 6; k0 >= 0; k0 -= 64) {
+        float r = first;
+        if (k0 > 0) r = rewards[(size_t)((hr + min(k0 + lane, m - 1)) % H) * B + b];
+        // at least one term a chunk: the loaded chunk is always consumed here, so no load
+        // of the fold is still in flight (as far as the compiler can tell) after it
+        int l = min(64, m - k0) - 1;
+        do {
+            const float rl = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(r), l));
+            acc = (double)rl + gamma * acc;
+            g *= gamma;
+        } while (--l >= 0);
+    }
+    if (lane == 0) {
+        *R = (float)acc;
+        *disc = (float)g;
+    }
+}
+
+// one thread per output float of s and s' (the last resort: any F, N and alignment);
+// a / R / steps / discount by the first threads. Every thread finds its sample's m.
+static __global__ void replay_nstep_kernel(const float* series, int T, int N, int F, int W, const int32_t* days,
+                                           const float* actions, const float* rewards, int H, int B,
+                                           const int32_t* h0, const int32_t* env, int S, NstepRing rg, float* s,
+                                           float* s_next, float* a_out, float* r_out, int32_t* steps,
+                                           float* discount) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t per = (int64_t)N * W * F;
+    const int Fm = F - 1;
+    if (i < (int64_t)S * N) {                     // a = actions[h0+W]; the fold by the sample's first thread
+        const int j = (int)(i / N), n = (int)(i % N);
+        const int b = env[j];
+        const int ha = (h0[j] + W) % H;
+        a_out[i] = actions[((size_t)ha * B + b) * N + n];
+        if (n == 0) {
+            const int m = nstep_count(rg, H, W, h0[j]);
+            steps[j] = m;
+            nstep_fold_serial(rewards, H, B, b, (h0[j] + W - 1) % H, m, rg.gamma, r_out + j, discount + j);
+        }
+    }
+    if (i >= (int64_t)S * per) return;
+    const int j = (int)(i / per);
+    int rem = (int)(i - (int64_t)j * per);
+    const int n = rem / (W * F);
+    rem -= n * W * F;
+    const int t = rem / F, f = rem - t * F;
+    const int b = env[j], hj = h0[j];
+    const int m = nstep_count(rg, H, W, hj);
+    float v, vn;
+    if (f < Fm) {
+        const int d = days[(size_t)((hj + W - 1) % H) * B + b] - (W - 1) + t;           // s: the window of h0
+        const int dn = days[(size_t)((hj + m + W - 2) % H) * B + b] + 1 - (W - 1) + t;  // s': one past h0+m-1's
+        v = (d >= 0 && d < T) ? series[((size_t)d * N + n) * Fm + f] : NAN;
+        vn = (dn >= 0 && dn < T) ? series[((size_t)dn * N + n) * Fm + f] : NAN;
+    } else {
+        v = actions[((size_t)((hj + t) % H) * B + b) * N + n];
+        vn = actions[((size_t)((hj + m + t) % H) * B + b) * N + n];
+    }
+    s[i] = v;
+    s_next[i] = vn;
+}
+
+// One workgroup per sample, any F: the days the pair spans are staged in LDS as
+// [N][D][F] (D = W + min(n, W) rows reserved). Where s' starts m <= W days after s the
+// two windows are one image of W + m days, every series line and action row fetched
+// once; otherwise (disjoint windows, or day indices that do not advance by one a row)
+// the image holds s, then s', in two passes.
+static __global__ __launch_bounds__(256) void replay_nstep_lds_kernel(const float* series, int T, int N, int F, int W,
+                                                               const int32_t* days, const float* actions,
+                                                               const float* rewards, int H, int B,
+                                                               const int32_t* h0, const int32_t* env, NstepRing rg,
+                                                               int D, float* s, float* s_next, float* a_out,
+                                                               float* r_out, int32_t* steps, float* discount) {
+    extern __shared__ __attribute__((aligned(16))) float ext[];
+    const int j = blockIdx.x, tid = threadIdx.x;
+    const int b = env[j], hj = h0[j];
+    const int Fm = F - 1;
+    const int m = nstep_count(rg, H, W, hj);                     // uniform: one sample per workgroup
+    const float rw = tid < min(m, 64) ? rewards[(size_t)((hj + W - 1 + tid) % H) * B + b] : 0.0f;
+    const int dA = days[(size_t)((hj + W - 1) % H) * B + b] - (W - 1);
+    const int dB = days[(size_t)((hj + m + W - 2) % H) * B + b] + 1 - (W - 1);
+    const bool joint = dB - dA == m && m <= D - W;
+    const int WF = W * F, per = N * WF;
+    float* so = s + (size_t)j * per;
+    float* sn = s_next + (size_t)j * per;
+    const bool vec = (per & 3) == 0;
+    auto stage = [&](int hA, int d0, int nd) {                   // t-major: a day's assets are contiguous
+        for (int it = tid; it < N * nd; it += 256) {
+            const int t = it / N, n = it - t * N;
+            const int d = d0 + t;
+            float* dst = ext + ((size_t)n * D + t) * F;
+            const bool in = d >= 0 && d < T;
+            const float* src = series + ((size_t)(in ? d : 0) * N + n) * Fm;
+            for (int f = 0; f < Fm; ++f) dst[f] = in ? src[f] : NAN;
+            dst[Fm] = actions[((size_t)((hA + t) % H) * B + b) * N + n];
+        }
+    };
+    auto emit = [&](float* out, int day0) {                      // image days day0 .. day0+W-1 -> [N, W, F]
+        if (vec) {
+            for (int q = tid; q < per / 4; q += 256) {
+                float v[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int e = 4 * q + k;
+                    const int n = e / WF, rem = e - n * WF;
+                    v[k] = ext[((size_t)n * D + day0) * F + rem];
+                }
+                reinterpret_cast<f4*>(out)[q] = f4{v[0], v[1], v[2], v[3]};
+            }
+        } else {
+            for (int e = tid; e < per; e += 256) {
+                const int n = e / WF, rem = e - n * WF;
+                out[e] = ext[((size_t)n * D + day0) * F + rem];
+            }
+        }
+    };
+    if (tid < N) a_out[(size_t)j * N + tid] = actions[((size_t)((hj + W) % H) * B + b) * N + tid];
+    if (joint) {
+        stage(hj, dA, W + m);
+        __syncthreads();
+        emit(so, 0);
+        emit(sn, m);
+    } else {
+        stage(hj, dA, W);
+        __syncthreads();
+        emit(so, 0);
+        __syncthreads();
+        stage((hj + m) % H, dB, W);
+        __syncthreads();
+        emit(sn, 0);
+    }
+    if (tid < 64) {
+        if (tid == 0) steps[j] = m;
+        nstep_fold_wave(rewards, H, B, b, (hj + W - 1) % H, m, rw, rg.gamma, r_out + j, discount + j);
+    }
+}
+
+// The F = 5 n-step gather, persistent like replay_gather_f5p_kernel: workgroup g takes
+// samples g, g + G, .. and runs them as a sequence of passes over one LDS image
+// [R][D][5] (D = W + min(n, W)):
+//   joint  (s' starts m <= W days after s): W + m days staged once, s from day 0, s' from day m
+//   first / second (disjoint windows, or days that do not advance by one a row): s, then s'
+// The next pass's staging loads — market float4s, actions and, for a sample's first
+// pass, its first 64 rewards in wave 0 — go out once the current image is in LDS, before
+// the write-out; wave 0 folds the current sample's rewards just before it issues them. The index chain runs three samples ahead, one memory level a sample:
+// env / h0, then the day of s with the two episode ids that decide m, then the day of s'.
+template <int PPT, int NT>
+__global__ __launch_bounds__(256) void replay_nstep_f5p_kernel(const float* __restrict__ series, int T, int N, int W,
+                                                               const int32_t* __restrict__ days,
+                                                               const float* __restrict__ actions,
+                                                               const float* __restrict__ rewards, int H, int B,
+                                                               const int32_t* __restrict__ h0,
+                                                               const int32_t* __restrict__ env, int S,
+                                                               NstepRing rg, int D, float* s, float* s_next,
+                                                               float* a_out, float* r_out, int32_t* steps,
+                                                               float* discount, int R, FastDiv div_r,
+                                                               FastDiv div_wf) {
+    constexpr int F = 5;
+    extern __shared__ __attribute__((aligned(16))) float ext[];
+    const int tid = threadIdx.x;
+    const int n0 = blockIdx.y * R;
+    const int WF = W * F, per = R * WF;
+    const int G = gridDim.x;
+    int j = blockIdx.x;
+    if (j >= S) return;                                    // uniform per workgroup
+    const auto rs_ser = make_rsrc(series, (uint32_t)T * (uint32_t)N * 16u);
+    const bool folds = tid < 64 && blockIdx.y == 0;        // wave 0 of the sample's first asset group
+    f4 mk[PPT];
+    float ac[PPT];
+    float rw = 0.0f;
+    // the staging loads of one pass, nothing waited: nd days from day d0 and ring row hA;
+    // mr > 0: the pass opens a sample of mr steps whose rewards start at row hr
+    // (a lane past the pass's pairs repeats the last pair's action load, as the one-step
+    // kernel does: a select on the loaded value would wait for every load in turn)
+    auto issue = [&](int bb, int hA, int d0, int nd, int mr, int hr) {
+        if (folds && mr > 0) rw = rewards[(size_t)ring_wrap(hr + min(tid, mr - 1), H) * B + bb];
+        const int P = R * nd;
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) {
+            const int it = min(tid + k * 256, P - 1);
+            const int t = (int)fdiv((uint32_t)it, div_r), n = n0 + it - t * R;
+            const int h = ring_wrap(hA + t, H);            // t < W + m <= H - 1
+            ac[k] = actions[((size_t)h * B + bb) * N + n];
+            const int d = d0 + t;
+            const bool in = tid + k * 256 < P && d >= 0 && d < T;
+            mk[k] = buf_load4(rs_ser, in ? ((uint32_t)d * (uint32_t)N + (uint32_t)n) * 16u : 0xFFFFFFF0u);
+        }
+    };
+    // rows below 2H; a NULL row_episode reads the day array instead and ignores the ids
+    auto day_at = [&](int bb, int row) { return days[(size_t)ring_wrap(row, H) * B + bb]; };
+    const bool has_ep = rg.row_ep != nullptr;
+    const int32_t* __restrict__ epp = has_ep ? rg.row_ep : days;
+    // index pipeline. c: the sample in hand, 1: the next (complete: b, h, m, dA, dB),
+    // 2: b, h, cap, the ids E / far and dA loaded (m follows without a load unless an
+    // episode ends inside the cap), 3: b, h
+    int bc, hc, mc, dAc, dBc;
+    int b1 = 0, h1 = 0, m1 = 1, dA1 = 0, dB1 = 0;
+    int b2 = 0, h2 = 0, nn2 = 1, E2 = 0, far2 = 0, dA2 = 0;
+    int b3 = 0, h3 = 0;
+    bool v1 = j + G < S, v2 = j + 2 * G < S, v3 = j + 3 * G < S;
+    auto level2 = [&](int bb, int hh, int& nn, int& E, int& far, int& dA) {    // three loads, no branch
+        nn = nstep_cap(rg, H, W, hh);
+        E = epp[hh];
+        far = epp[nstep_last_row(H, W, hh, nn)];
+        dA = day_at(bb, hh + W - 1) - (W - 1);
+    };
+    auto finish = [&](int hh, int nn, int E, int far) { return has_ep ? nstep_finish(rg, H, W, hh, nn, E, far) : nn; };
+    auto level3 = [&](int bb, int hh, int mm) { return day_at(bb, hh + mm + W - 2) + 1 - (W - 1); };
+    bc = env[j]; hc = h0[j];
+    if (v1) { b1 = env[j + G]; h1 = h0[j + G]; }
+    if (v2) { b2 = env[j + 2 * G]; h2 = h0[j + 2 * G]; }
+    if (v3) { b3 = env[j + 3 * G]; h3 = h0[j + 3 * G]; }
+    {
+        int nn, E, far;
+        level2(bc, hc, nn, E, far, dAc);
+        mc = finish(hc, nn, E, far);
+        dBc = level3(bc, hc, mc);
+        if (v1) {
+            level2(b1, h1, nn, E, far, dA1);
+            m1 = finish(h1, nn, E, far);
+            dB1 = level3(b1, h1, m1);
+        }
+        if (v2) level2(b2, h2, nn2, E2, far2, dA2);
+    }
+    bool joint = dBc - dAc == mc && mc <= D - W;
+    int pass = joint ? 0 : 1;                              // 0 joint, 1 first (s), 2 second (s')
+    issue(bc, hc, dAc, joint ? W + mc : W, mc, ring_wrap(hc + W - 1, H));
+    while (true) {
+        const int nd = pass == 0 ? W + mc : W;
+        const int dfirst = pass == 2 ? dBc : dAc;
+        if (pass != 2 && tid < R)
+            a_out[(size_t)j * N + n0 + tid] = actions[((size_t)ring_wrap(hc + W, H) * B + bc) * N + n0 + tid];
+        const int P = R * nd;
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) {
+            const int it = tid + k * 256;
+            if (it < P) {
+                const int t = (int)fdiv((uint32_t)it, div_r), nl = it - t * R;
+                const int d = dfirst + t;
+                const bool in = d >= 0 && d < T;
+                float* dst = ext + ((size_t)nl * D + t) * F;
+                dst[0] = in ? mk[k].x : NAN;
+                dst[1] = in ? mk[k].y : NAN;
+                dst[2] = in ? mk[k].z : NAN;
+                dst[3] = in ? mk[k].w : NAN;
+                dst[4] = ac[k];
+            }
+        }
+        __syncthreads();
+        // the fold sits here, where nothing this wave waits for is in flight but the last
+        // write-out's stores: behind the next pass's loads its waits would be theirs.
+        // Wave 0 then issues its share of them late, with the whole write-out to land in
+        if (pass != 2 && folds) {
+            if (tid == 0) steps[j] = mc;
+            nstep_fold_wave(rewards, H, B, bc, ring_wrap(hc + W - 1, H), mc, rw, rg.gamma, r_out + j, discount + j);
+        }
+        // the next pass's loads fly during the write-out
+        const bool last_of_sample = pass != 1;
+        if (pass == 1) {
+            issue(bc, ring_wrap(hc + mc, H), dBc, W, 0, 0);
+        } else if (v1) {
+            const bool jn = dB1 - dA1 == m1 && m1 <= D - W;
+            issue(b1, h1, dA1, jn ? W + m1 : W, m1, ring_wrap(h1 + W - 1, H));
+        }
+        float* so = s + (size_t)j * N * WF + (size_t)n0 * WF;
+        float* sn = s_next + (size_t)j * N * WF + (size_t)n0 * WF;
+        const auto rso = make_rsrc(so, (uint32_t)per * 4u), rsn = make_rsrc(sn, (uint32_t)per * 4u);
+        const int skip = (D - W) * F;                      // LDS row n starts n*skip floats later than in s
+        if (pass == 0) {
+            const int off = mc * F;
+            for (int q = tid; q < per / 4; q += 256) {
+                float v0[4], vn[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int e = 4 * q + k;
+                    const int n = (int)fdiv((uint32_t)e, div_wf);
+                    const float* x = ext + (__umul24(n, skip) + e);   // 24-bit multiply: full rate
+                    v0[k] = x[0];
+                    vn[k] = x[off];
+                }
+                buf_store4<NT>(rso, (uint32_t)q * 16u, f4{v0[0], v0[1], v0[2], v0[3]});
+                buf_store4<NT>(rsn, (uint32_t)q * 16u, f4{vn[0], vn[1], vn[2], vn[3]});
+            }
+        } else {
+            const auto rs_out = pass == 1 ? rso : rsn;
+            for (int q = tid; q < per / 4; q += 256) {
+                float v0[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int e = 4 * q + k;
+                    const int n = (int)fdiv((uint32_t)e, div_wf);
+                    v0[k] = ext[__umul24(n, skip) + e];
+                }
+                buf_store4<NT>(rs_out, (uint32_t)q * 16u, f4{v0[0], v0[1], v0[2], v0[3]});
+            }
+        }
+        if (!last_of_sample) {
+            __syncthreads();                               // the image is rewritten next
+            pass = 2;
+            continue;
+        }
+        // index chain ahead, one level each: sample 2 completes (its ids and dA were
+        // loaded a sample ago), sample 3 loads its ids and dA, sample 4 its env / h0. Six
+        // loads in one block without a branch (a slot past S holds row 0 of env 0), so one
+        // round trip covers them
+        const int j4 = j + 4 * G;
+        const bool v4 = j4 < S;
+        const int m2 = finish(h2, nn2, E2, far2);
+        const int dB2 = level3(b2, h2, m2);
+        int nn3, E3, far3, dA3;
+        level2(b3, h3, nn3, E3, far3, dA3);
+        const int b4 = env[min(j4, S - 1)], h4 = h0[min(j4, S - 1)];
+        __syncthreads();                                   // the image is rewritten next
+        if (!v1) break;
+        j += G;
+        bc = b1; hc = h1; mc = m1; dAc = dA1; dBc = dB1;
+        b1 = b2; h1 = h2; m1 = m2; dA1 = dA2; dB1 = dB2; v1 = v2;
+        b2 = b3; h2 = h3; nn2 = nn3; E2 = E3; far2 = far3; dA2 = dA3; v2 = v3;
+        b3 = b4; h3 = h4; v3 = v4;
+        pass = (dBc - dAc == mc && mc <= D - W) ? 0 : 1;
     }
 }
 

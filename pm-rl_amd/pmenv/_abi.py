@@ -13,8 +13,9 @@ import torch  # noqa: F401
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PMENV_LIB", os.path.join(HERE, "libpmenv.so"))
 
-PMENV_ABI_VERSION = 3   # 2: pmenv_window_written / pmenv_state_written; cfg default ret_mode GROSS
+PMENV_ABI_VERSION = 4   # 2: pmenv_window_written / pmenv_state_written; cfg default ret_mode GROSS
                         # 3: pmenv_step_host / pmenv_reset_host
+                        # 4: pmenv_replay_gather_nstep
 
 # enums (include/pmenv.h)
 REWARD_KINDS = {"log_returns": 0, "returns": 1, "sharpe_ratio": 2, "diff_sharpe": 3}
@@ -91,6 +92,9 @@ SIGNATURES = [
     ("pmenv_moments", ctypes.c_int, [_P, _I64, _P, _P, _P]),
     ("pmenv_replay_gather", ctypes.c_int,
      [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I32, _P, _P, _P, _P, _P]),
+    ("pmenv_replay_gather_nstep", ctypes.c_int,
+     [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, _F,
+      _P, _P, _P, _P, _P, _P, _P]),
     ("pmenv_rollout_gather", ctypes.c_int,
      [_P, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _P, _P]),
     ("pmenv_metrics", ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, ctypes.c_double, ctypes.c_double, _P, _P]),

@@ -11,6 +11,8 @@ and the evaluation metrics all on device.
     buffer.add(epoch, step, a, r)        :69     replay.add(day - 1, a, r)             (DeviceReplay)
     s, a, r, s_ = buffer.sample()        :91     replay.sample(batch_size)             (HIP gather)
     agent.update(epoch, step, s, a, r, s_) :92   update(s, a, r, s_)                   (caller's agent)
+    add_experience's n_step fold (td3.py:85-106) replay.sample_nstep(batch_size, n)    (n_step > 1: HIP gather,
+                                                 update(s, a, R, s_, discount)          folded at sample time)
     metrics.write()                      :110    trajectory_metrics(...)               (HIP reductions)
 
 Every env trades the one HBM-resident series (pmenv.data.MarketSeries) from its own
@@ -24,10 +26,16 @@ from .replay import DeviceReplay, trajectory_metrics
 
 
 class OffPolicy:
-    def __init__(self, env, series, capacity, act=None, update=None, batch_size=256, generator=None):
+    def __init__(self, env, series, capacity, act=None, update=None, batch_size=256, generator=None,
+                 n_step=1, gamma=0.997):
         """env: a pmenv.TradingEnv over B envs; series: pmenv.data.MarketSeries [T, N, F-1];
         capacity: replay steps kept per env (buffer.py's ring); act(obs [B, N, W, F]) ->
-        [B, N] weights; update(s, a, r, s_) -> anything (one agent update)."""
+        [B, N] weights; update(s, a, r, s_) -> anything (one agent update). n_step > 1
+        (agent/td3/td3.py:85-106; gamma: config/dsac.py:30): update(s, a, R, s_, discount)
+        with R the discounted sum of up to n_step rewards, s_ the state after the last of
+        them and discount [S] = gamma ** (rewards folded), the factor of the bootstrap term."""
+        if n_step < 1 or not 0.0 < gamma <= 1.0:
+            raise ValueError("n_step must be >= 1 and gamma in (0, 1]")
         cfg = env.cfg
         if series.num_assets != cfg.num_assets or series.channels != cfg.features - 1:
             raise ValueError("series must be [T, num_assets, features - 1]")
@@ -37,6 +45,7 @@ class OffPolicy:
         self.act_fn, self.update_fn = act, update
         self.batch_size = batch_size
         self.generator = generator
+        self.n_step, self.gamma = n_step, gamma
 
     def _random_action(self):
         """agent.act(s, is_random=True): uniform random portfolio weights (a simplex point)."""
@@ -71,6 +80,11 @@ class OffPolicy:
         """_update_off_policy (off_policy.py:88-94): `steps` sampled batches into update()."""
         out = []
         for _ in range(steps):
+            if self.n_step > 1:
+                s, a, r, s_, _, disc = self.replay.sample_nstep(self.batch_size, self.n_step, self.gamma,
+                                                                self.generator)
+                out.append(self.update_fn(s, a, r, s_, disc) if self.update_fn is not None else None)
+                continue
             s, a, r, s_ = self.replay.sample(self.batch_size, self.generator)
             out.append(self.update_fn(s, a, r, s_) if self.update_fn is not None else None)
         return out

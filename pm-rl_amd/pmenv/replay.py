@@ -36,6 +36,26 @@ def valid_starts(row_episode, oldest, count, W, H):
     return np.flatnonzero(chrono[:span] == chrono[W:W + span])
 
 
+def nstep_counts(row_episode, oldest, count, W, H, st, n):
+    """The number of transitions m an n-step sample folds, for starts `st` (offsets from the
+    oldest recorded row, each a valid one-step start): the largest m in [1, n] such that
+    the one-step samples at st, st+1, .., st+m-1 are all valid — st+m-1 < count - W - 1 and
+    rows st .. st+m-1+W in one episode. This is where agent/td3/td3.py:94-97 stops folding
+    at `done`: an episode boundary or the newest recorded rows end the sum early."""
+    st = np.asarray(st, dtype=np.int64)
+    span = max(count - W - 1, 0)
+    chrono = np.roll(np.asarray(row_episode), -oldest)[:count]    # rows oldest .. newest
+    ok = np.zeros(span + 1, dtype=bool)                           # ok[span] = False: the newest rows end a run
+    for k in range(span):
+        ok[k] = np.all(chrono[k:k + W + 1] == chrono[k])
+    run = np.zeros(span + 1, dtype=np.int64)                      # valid starts in a row from k on
+    for k in range(span - 1, -1, -1):
+        run[k] = run[k + 1] + 1 if ok[k] else 0
+    if st.size and (st.min() < 0 or st.max() >= span or not ok[st].all()):
+        raise ValueError("st holds a start that is not a valid one-step sample")
+    return np.minimum(run[st], n).astype(np.int32)
+
+
 class DeviceReplay:
     def __init__(self, num_envs, num_assets, window, capacity, series, features=5):
         if capacity < window + 2:
@@ -53,6 +73,9 @@ class DeviceReplay:
         self._row_ep = np.zeros(capacity, dtype=np.int64)
         self._starts = None           # device tensor of valid starts when some windows straddle episodes
         self._starts_key = None
+        # the same ids on the device for the n-step gather, uploaded when a sample finds them stale
+        self._row_ep_dev = torch.zeros(capacity, dtype=torch.int32, device=dev)
+        self._row_ep_dirty = False
 
     def __len__(self):
         return self.count
@@ -68,6 +91,7 @@ class DeviceReplay:
         self.days[h].copy_(torch.as_tensor(day).reshape(self.B))
         self.actions[h].copy_(torch.as_tensor(action).reshape(self.B, self.N))
         self.rewards[h].copy_(torch.as_tensor(reward).reshape(self.B))
+        self._row_ep_dirty |= self._row_ep[h] != self.episode
         self._row_ep[h] = self.episode
         self.head = (h + 1) % self.H
         self.count = min(self.count + 1, self.H)
@@ -122,6 +146,40 @@ class DeviceReplay:
 
     def sample(self, batch_size, generator=None):
         return self.gather(*self.indices(batch_size, generator))
+
+    def gather_nstep(self, h0, env, n_step, gamma):
+        """The n-step transition of agent/td3/td3.py:85-106 for the given one-step samples:
+        (s, a, R, s_next, steps, discount). s and a are `gather`'s; R folds the rewards of
+        the m = steps[j] <= n_step transitions from h0 on, R = sum_k gamma^k r_k; s_next is
+        the next state of the last folded one; discount = gamma^m is what the caller's
+        bootstrap term takes. The fold stops where td3's `done` would: at an episode
+        boundary and at the newest recorded rows (`nstep_counts`)."""
+        lib = _abi.load()
+        S = h0.numel()
+        dev = self.days.device
+        if self._row_ep_dirty:
+            self._row_ep_dev.copy_(torch.from_numpy(self._row_ep.astype(np.int32)))
+            self._row_ep_dirty = False
+        s = torch.empty(S, self.N, self.W, self.F, device=dev)
+        s2 = torch.empty_like(s)
+        a = torch.empty(S, self.N, device=dev)
+        r = torch.empty(S, device=dev)
+        steps = torch.empty(S, dtype=torch.int32, device=dev)
+        disc = torch.empty(S, device=dev)
+        sb = self.series.bars
+        oldest = (self.head - self.count) % self.H
+        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _abi.check(lib.pmenv_replay_gather_nstep(_p(sb), sb.shape[0], self.N, self.F, self.W, _p(self.days),
+                                                 _p(self.actions), _p(self.rewards), self.H, self.B,
+                                                 _p(h0.contiguous()), _p(env.contiguous()), S,
+                                                 _p(self._row_ep_dev), oldest, self.count, int(n_step), float(gamma),
+                                                 _p(s), _p(s2), _p(a), _p(r), _p(steps), _p(disc), st),
+                   None, "pmenv_replay_gather_nstep")
+        return s, a.reshape(S, self.N, 1), r.reshape(S, 1, 1), s2, steps, disc
+
+    def sample_nstep(self, batch_size, n_step, gamma=0.997, generator=None):
+        """`sample` with n-step returns (gamma: config/dsac.py:30)."""
+        return self.gather_nstep(*self.indices(batch_size, generator), n_step, gamma)
 
 
 def trajectory_metrics(returns, values, weights, risk_free_rate=RISK_FREE_RATE, periods=252):

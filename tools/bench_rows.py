@@ -258,6 +258,33 @@ def main():
                 os.environ["PMENV_REPLAY_LDS"] = "1"
             res.append(row(f"replay_gather_{mode}", timeit(gather, a.reps), alg, S=S, N=N, W=W))
         os.environ.pop("PMENV_REPLAY_LDS", None)
+        del rb
+        # n-step gather beside the one-step gather at config 3's shape (16,384 envs x 30 x 50 x 5,
+        # S = 8,192), same process, same indices: the one-step time and its repeats' spread,
+        # then n = 1, 5, 64 as ratios to it
+        B = 16384
+        rb = DeviceReplay(B, N, W, H, ms)
+        for h in range(H):
+            rb.add(torch.full((B,), W + h, dtype=torch.int32, device=dev), torch.rand(B, N, device=dev),
+                   torch.randn(B, device=dev))
+        h0, e = rb.indices(S, generator=torch.Generator().manual_seed(2))
+        stp = torch.empty(S, dtype=torch.int32, device=dev)
+        dsc = torch.empty(S, device=dev)
+        oldest = (rb.head - rb.count) % H
+
+        def gather_n(n):
+            ck(lib.pmenv_replay_gather_nstep(P(sb), sb.shape[0], N, 5, W, P(rb.days), P(rb.actions), P(rb.rewards),
+                                             H, B, P(h0), P(e), S, P(rb._row_ep_dev), oldest, rb.count, n, 0.997,
+                                             P(s_), P(s2), P(ao), P(ro), P(stp), P(dsc), st), "gather_nstep")
+        reps1 = [timeit(gather, a.reps) for _ in range(5)]
+        one = statistics.median(reps1)
+        res.append(row("replay_gather_config3", one, alg, S=S, N=N, W=W, B=B,
+                       spread=round((max(reps1) - min(reps1)) / one, 4)))
+        for n in (1, 5, 64):
+            us = statistics.median([timeit(lambda: gather_n(n), a.reps) for _ in range(5)])
+            gather_n(n)
+            res.append(row(f"replay_gather_nstep_n{n}", us, alg, S=S, N=N, W=W, B=B, n=n, ratio=round(us / one, 4),
+                           mean_steps=round(float(stp.float().mean()), 2)))
         del rb, s_, s2
         for T, B in ((252, 65536), (252, 4096)):
             rets = 0.001 * torch.randn(T, B, device=dev, dtype=torch.float64, generator=g)
