@@ -37,6 +37,8 @@ extern "C" {
  *    kind; was AUTO in 1) */
 /* 3: pmenv_step_host / pmenv_reset_host (host buffers, the reference driver's call shape) */
 /* 4: pmenv_replay_gather_nstep (n-step return samples of the replay ring) */
+/*    (pmenv_replay_gather_seq, sequence samples of the same ring, was added under 4: a new
+ *    symbol breaks no caller; pmenv's loader names a symbol that a stale library lacks) */
 #define PMENV_ABI_VERSION 4
 
 /* Opaque HIP stream (identical to HIP's own typedef); NULL = default stream. */
@@ -416,6 +418,26 @@ int pmenv_replay_gather_nstep(const float* series, int32_t T, int32_t N, int32_t
                               int32_t oldest, int32_t count, int32_t n, float gamma,
                               float* s, float* s_next, float* a_out, float* r_out,
                               int32_t* steps, float* discount, hipStream_t stream);
+
+/* Sequence samples of the same ring (agent/dreamer/dreamer.py:77-80 trains on sequences of
+ * consecutive steps; world_model.py:41-64 walks them time-major). Element t of sequence j
+ * is the one-step sample at start (h0[j] + t) mod H of env[j] as pmenv_replay_gather
+ * defines it: x = its s, a_out = its a_out (actions[h0+t+W]), r_out = its r_out
+ * (rewards[h0+t+W-1]). length [S] = m, the n-step count of pmenv_replay_gather_nstep with
+ * n = L: an episode boundary or the newest rows cut a sequence short. Elements t >= m are
+ * written as +0.0 in x, a_out and r_out. Each element takes the window ending at its own
+ * days[h0+t+W-1], so a ring whose day indices skip is served too; days outside the series
+ * read NaN. time_major != 0: x [L, S, N, W, F], a_out [L, S, N], r_out [L, S] (Dreamer's
+ * order); time_major == 0: x [S, L, N, W, F], a_out [S, L, N], r_out [S, L]. Enqueues on
+ * `stream`; never synchronises, allocates or frees. PMENV_ERR_ARG: L < 1, count > H,
+ * oldest outside [0, H), a NULL pointer other than row_episode, the shape errors of
+ * pmenv_replay_gather_nstep. */
+int pmenv_replay_gather_seq(const float* series, int32_t T, int32_t N, int32_t F, int32_t W,
+                            const int32_t* days, const float* actions, const float* rewards,
+                            int32_t H, int32_t B, const int32_t* h0, const int32_t* env, int32_t S,
+                            const int32_t* row_episode /* [H], NULL = one episode */,
+                            int32_t oldest, int32_t count, int32_t L, int32_t time_major,
+                            float* x, float* a_out, float* r_out, int32_t* length, hipStream_t stream);
 
 /* The compact on-policy rollout (replay/rollout_buffer.py:43-57 stores s per step;
  * here the windows are re-materialised instead): for each of the S

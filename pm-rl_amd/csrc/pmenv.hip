@@ -1451,6 +1451,97 @@ int pmenv_replay_gather_nstep(const float* series, int32_t T, int32_t N, int32_t
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
 
+int pmenv_replay_gather_seq(const float* series, int32_t T, int32_t N, int32_t F, int32_t W, const int32_t* days,
+                            const float* actions, const float* rewards, int32_t H, int32_t B, const int32_t* h0,
+                            const int32_t* env, int32_t S, const int32_t* row_episode, int32_t oldest, int32_t count,
+                            int32_t L, int32_t time_major, float* x, float* a_out, float* r_out, int32_t* length,
+                            hipStream_t stream) {
+    if (!series || !days || !actions || !rewards || !h0 || !env || !x || !a_out || !r_out || !length || T < 1 ||
+        N < 1 || F < 2 || W < 1 || H < W + 1 || B < 1 || S < 1 || L < 1 || count < 0 || count > H || oldest < 0 ||
+        oldest >= H)
+        return PMENV_ERR_ARG;
+    const NstepRing rg{row_episode, oldest, count, L, 1.0};
+    static int cus = 0;                                    // one workgroup per CU, as the other gathers
+    if (!cus) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+            cus = 256;
+    }
+    int policy = -1, lc_knob = 0;
+    pmenv_tools::replay_seq_knobs(&policy, &lc_knob);
+    // F = 5 fast form (replay_seq_f5p_kernel): asset groups of R rows by the n-step rule — R
+    // divides N, R*W*F is a multiple of 4, at most 12 (day, asset) pairs per thread, the
+    // image [R][W + Lc][5] (+16 B) within 64 KiB — sized so that a chunk holds min(L, 8)
+    // elements, or one where no group does. Lc, the elements per chunk: 8 where the image
+    // holds them, fewer where that leaves a CU without an item (Dreamer's 16 sequences of 64
+    // elements: 4). Measured on config 3's ring: 128 x 64 (nt stores) takes 69 us at Lc = 4
+    // and 8, 72-73 us at 16 and 32, 98 us at 2, 159 us at 1; 16 x 64 (sc1 stores) takes
+    // 10.0 us at 4, 13.4-14.0 us at 2 and 8, 21-37 us at 1, 16 and 32 (tools/bench_rows.py's
+    // PMENV_SEQ_LC rows, profiles/rows_seq_ab.json).
+    const bool al16 = (((uintptr_t)x | (uintptr_t)series) & 15u) == 0;
+    auto group = [&](int lc) {
+        const int64_t D = (int64_t)W + lc;
+        for (int r = N < 256 ? N : 256; r >= 1; --r)
+            if (N % r == 0 && ((int64_t)r * W * F) % 4 == 0 && r * D <= 12 * 256 &&
+                (r * D * F + 4) * sizeof(float) <= 64 * 1024)
+                return r;
+        return 0;
+    };
+    int R = 0;
+    if (F == 5 && al16) {
+        R = group(L < 8 ? L : 8);
+        if (!R) R = group(1);
+    }
+    const int gy = R ? N / R : 1;
+    if (R > 0 && (int64_t)S * gy * L <= (1 << 30)) {
+        int64_t cap = 12 * 256 / R;
+        if (cap > (64 * 1024 / 4 - 4) / (F * R)) cap = (64 * 1024 / 4 - 4) / (F * R);
+        cap -= W;
+        if (cap > 256) cap = 256;
+        if (cap > L) cap = L;
+        int64_t nc = (L + (cap < 8 ? cap : 8) - 1) / (cap < 8 ? cap : 8);
+        const int64_t want = ((int64_t)cus + (int64_t)S * gy - 1) / ((int64_t)S * gy);   // chunks for an item a CU
+        if (nc < want) nc = want < L ? want : L;
+        int Lc = (int)((L + nc - 1) / nc);
+        if (lc_knob > 0) Lc = (int)(lc_knob < cap ? lc_knob : cap);
+        nc = (L + Lc - 1) / Lc;
+        const int items = (int)((int64_t)S * gy * nc);
+        const int D = W + Lc, pairs = R * D;
+        const size_t glds = ((size_t)R * D * F + 4) * sizeof(float);
+        // the windows are written once and read by the learner later: the rollout gather's
+        // rule — sc1 stores while they fit the Infinity Cache, nt stores above — with the
+        // bound where this kernel was measured: 31 MB (16 x 64) 21.7 us sc1, 23.2 nt, 24.4
+        // plain; 245 MB (128 x 64) 50.7 us sc1, 57.2 plain, 69.0 nt (PMENV_SEQ_NT rows,
+        // profiles/rows_seq_ab.json). Above 256 MiB nothing was measured for this kernel:
+        // nt, as the rollout gather's sc1 loses there
+        if (policy < 0) policy = (size_t)S * L * N * W * F * sizeof(float) <= ((size_t)256 << 20) ? 16 : 2;
+        const FastDiv dr = make_fastdiv((uint32_t)R), dwf = make_fastdiv((uint32_t)(W * F));
+        const FastDiv dnc = make_fastdiv((uint32_t)nc), dgy = make_fastdiv((uint32_t)gy);
+        const unsigned grid = (unsigned)(items < cus ? items : cus);
+        const int ppt = pairs <= 2 * 256 ? 2 : pairs <= 4 * 256 ? 4 : pairs <= 8 * 256 ? 8 : 12;
+#define PMENV_RSQ(PPT, NTV)                                                                                       \
+    replay_seq_f5p_kernel<PPT, NTV><<<grid, 256, glds, stream>>>(series, T, N, W, days, actions, rewards, H, B, h0, \
+                                                                 env, S, rg, Lc, (int)nc, time_major, x, a_out,     \
+                                                                 r_out, length, R, dr, dwf, dnc, dgy)
+#define PMENV_RSQ_P(NTV)                                                                                          \
+    do {                                                                                                          \
+        if (ppt == 2) PMENV_RSQ(2, NTV); else if (ppt == 4) PMENV_RSQ(4, NTV);                                    \
+        else if (ppt == 8) PMENV_RSQ(8, NTV); else PMENV_RSQ(12, NTV);                                            \
+    } while (0)
+        if (policy == 16) PMENV_RSQ_P(16); else if (policy == 2) PMENV_RSQ_P(2); else PMENV_RSQ_P(0);
+#undef PMENV_RSQ_P
+#undef PMENV_RSQ
+    } else {
+        const int64_t threads = (int64_t)S * L * N * W * F;
+        const int64_t blocks = (threads + 255) / 256;
+        if (blocks > 0x7FFFFFFF) return PMENV_ERR_ARG;
+        replay_seq_kernel<<<(unsigned)blocks, 256, 0, stream>>>(series, T, N, F, W, days, actions, rewards, H, B, h0,
+                                                               env, S, rg, time_major, x, a_out, r_out, length);
+    }
+    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
 int pmenv_rollout_gather(const float* series, int32_t T, int32_t N, int32_t F, int32_t W, const int32_t* start,
                          const float* weights, int32_t T_rec, int32_t B, int32_t ring_mode, const int32_t* t_idx,
                          const int32_t* env, int32_t S, float* s, hipStream_t stream) {
@@ -1613,6 +1704,7 @@ __attribute__((weak, noinline)) bool replay_gather(const float*, int32_t, int32_
                                                    hipStream_t, int*) {
     return false;
 }
+__attribute__((weak, noinline)) void replay_seq_knobs(int*, int*) {}
 __attribute__((weak, noinline)) bool rollout_gather(const float*, int32_t, int32_t, int32_t, int32_t, const int32_t*,
                                                     const float*, int32_t, int32_t, int32_t, const int32_t*,
                                                     const int32_t*, int32_t, float*, hipStream_t, int*) {

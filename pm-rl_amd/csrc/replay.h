@@ -9,7 +9,8 @@
 //   a  = actions[h0+W, b],  r = rewards[h0+W-1, b]                (buffer.py:59-72)
 // from the resident market series [T, N, F-1]. Recorded steps are a ring of H rows.
 // The replay_nstep_* kernels fold up to n such transitions into one at sample time
-// (agent/td3/td3.py:85-106): see "n-step samples" below.
+// (agent/td3/td3.py:85-106): see "n-step samples" below. The replay_seq_* kernels serve
+// sequences of consecutive samples (agent/dreamer/dreamer.py:77-80): "sequence samples".
 //
 // metrics_kernel restates util/eval.py:14-37 per env over a [T, B] trajectory with
 // quantstats' published definitions (quantstats is not installed here: parity unpinned).
@@ -957,6 +958,254 @@ __global__ __launch_bounds__(256) void replay_nstep_f5p_kernel(const float* __re
         b2 = b3; h2 = h3; nn2 = nn3; E2 = E3; far2 = far3; dA2 = dA3; v2 = v3;
         b3 = b4; h3 = h4; v3 = v4;
         pass = (dBc - dAc == mc && mc <= D - W) ? 0 : 1;
+    }
+}
+
+// ---------------------------------------------------------------- sequence samples
+// agent/dreamer/dreamer.py:77-80 trains its world model on sequences of consecutive
+// steps (world_model.py:41-64 walks them time-major). Element t of sequence j is the
+// one-step sample at start (h0[j] + t) mod H of env[j]: x = its s, a = its a_out, r = its
+// r_out. length[j] = m is the n-step count with n = L (NstepRing.n holds L): an episode
+// boundary or the newest recorded rows cut a sequence short, and the elements t >= m are
+// written as +0.0. e(j, t) = t*S + j (time-major) or j*L + t is the element's slot in
+// x [.., N, W, F], a_out [.., N] and r_out [..].
+
+// one thread per output float of x (any F, N and alignment, and rings whose day indices
+// skip: every element looks up its own day); a / r / length by the first threads
+static __global__ void replay_seq_kernel(const float* series, int T, int N, int F, int W, const int32_t* days,
+                                         const float* actions, const float* rewards, int H, int B,
+                                         const int32_t* h0, const int32_t* env, int S, NstepRing rg, int time_major,
+                                         float* x, float* a_out, float* r_out, int32_t* length) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int L = rg.n, Fm = F - 1;
+    const int64_t per = (int64_t)N * W * F;
+    auto slot = [&](int64_t e, int& j, int& t) {       // element slot -> (sequence, position)
+        if (time_major) { t = (int)(e / S); j = (int)(e - (int64_t)t * S); }
+        else { j = (int)(e / L); t = (int)(e - (int64_t)j * L); }
+    };
+    if (i < (int64_t)S * L * N) {                       // a = actions[h0+t+W], r = rewards[h0+t+W-1]
+        const int64_t e = i / N;
+        const int n = (int)(i - e * N);
+        int j, t;
+        slot(e, j, t);
+        const int b = env[j], hj = h0[j];
+        const int m = nstep_count(rg, H, W, hj);
+        const bool live = t < m;                        // t < m <= H: the rows below stay under 3H
+        a_out[i] = live ? actions[((size_t)ring_wrap(ring_wrap(hj + W + t, H), H) * B + b) * N + n] : 0.0f;
+        if (n == 0) {
+            r_out[e] = live ? rewards[(size_t)ring_wrap(ring_wrap(hj + W - 1 + t, H), H) * B + b] : 0.0f;
+            if (t == 0) length[j] = m;
+        }
+    }
+    if (i >= (int64_t)S * L * per) return;
+    const int64_t e = i / per;
+    int rem = (int)(i - e * per);
+    int j, t;
+    slot(e, j, t);
+    const int n = rem / (W * F);
+    rem -= n * W * F;
+    const int p = rem / F, f = rem - p * F;
+    const int b = env[j], hj = h0[j];
+    float v = 0.0f;
+    if (t < nstep_count(rg, H, W, hj)) {
+        const int ht = ring_wrap(hj + t, H);            // the element's one-step start
+        if (f < Fm) {
+            const int d = days[(size_t)ring_wrap(ht + W - 1, H) * B + b] - (W - 1) + p;
+            v = (d >= 0 && d < T) ? series[((size_t)d * N + n) * Fm + f] : NAN;
+        } else {
+            v = actions[((size_t)ring_wrap(ht + p, H) * B + b) * N + n];
+        }
+    }
+    x[i] = v;
+}
+
+// The F = 5 sequence gather, persistent (one workgroup per CU). A work item is (sequence j,
+// asset group g of R rows, chunk c of Lc elements); workgroup w takes items w, w + G, ..
+// The item's live elements (cnt = those below m) share ONE LDS image [R][D][5], D = W + Lc:
+// W + cnt - 1 series days (16-B loads) and W + cnt action rows, the last row for a_out
+// alone. Element t's [R, W, 5] block is the image shifted by t days, i.e. by 5t floats in
+// every asset row, so the windows leave as 16-B global stores whose four floats are read
+// from LDS one dword each: the shift is 20t bytes, 16-B aligned only for t % 4 == 0, and
+// dword reads run at 128 B/clk/CU, far above what one CU's share of the write stream asks.
+// The source offsets of a lane's quad are computed once and reused for every element.
+// Elements >= m take the same stores with zeros. The next item's staging loads go out once
+// the current image is in LDS, before the write-out. Its indices are resolved one item
+// earlier still: env / h0 of the item after next are loaded during a write-out, and after
+// it the episode ids that give m and the chunk's day indices. A chunk whose days do not
+// advance by one a row (a caller's own ring) is staged and written element by element.
+// NT: cache-policy bits of the window stores (0 plain, 2 nt, 16 sc1).
+template <int PPT, int NT>
+__global__ __launch_bounds__(256) void replay_seq_f5p_kernel(const float* __restrict__ series, int T, int N, int W,
+                                                             const int32_t* __restrict__ days,
+                                                             const float* __restrict__ actions,
+                                                             const float* __restrict__ rewards, int H, int B,
+                                                             const int32_t* __restrict__ h0,
+                                                             const int32_t* __restrict__ env, int S, NstepRing rg,
+                                                             int Lc, int nc, int time_major, float* x, float* a_out,
+                                                             float* r_out, int32_t* length, int R, FastDiv div_r,
+                                                             FastDiv div_wf, FastDiv div_nc, FastDiv div_gy) {
+    constexpr int F = 5;
+    extern __shared__ __attribute__((aligned(16))) float ext[];
+    int* flg = reinterpret_cast<int*>(ext);                // [4] each wave's verdict on a chunk's days
+    float* img = ext + 4;
+    const int tid = threadIdx.x, G = gridDim.x;
+    const int L = rg.n, gy = N / R, D = W + Lc;
+    const int WF = W * F, per = R * WF, skip = Lc * F;     // LDS row n starts n*skip floats later than in x
+    const int items = S * gy * nc;
+    if ((int)blockIdx.x >= items) return;                  // uniform per workgroup
+    const auto rs_ser = make_rsrc(series, (uint32_t)T * (uint32_t)N * 16u);
+    const bool has_ep = rg.row_ep != nullptr;
+    const int32_t* __restrict__ epp = has_ep ? rg.row_ep : days;
+    // an item: its sequence, group and chunk; env and start; m; the live elements of the
+    // chunk; the first staged day; whether the chunk's days advance by one a row
+    struct Item {
+        int j, n0, t0, b, h, m, cnt, dA, one;
+    };
+    auto raw = [&](int i, Item& it) {                      // env / h0: the first level of the chain
+        const int sg = (int)fdiv((uint32_t)i, div_nc);
+        it.j = (int)fdiv((uint32_t)sg, div_gy);
+        it.n0 = (sg - it.j * gy) * R;
+        it.t0 = (i - sg * nc) * Lc;
+        it.b = env[it.j];
+        it.h = h0[it.j];
+    };
+    // the second level: two episode ids, the chunk's first day and this thread's day, one
+    // round trip; then a verdict through LDS (two barriers: the image may be rewritten after)
+    auto resolve = [&](Item& it) {
+        const int nn = nstep_cap(rg, H, W, it.h);          // m <= nn <= count - W - 1 < H
+        const int tc = min(it.t0, nn - 1);                 // a chunk past nn is empty: any rows do
+        const int span = min(Lc, nn - tc);
+        const int row0 = ring_wrap(ring_wrap(it.h + W - 1, H) + tc, H);
+        const int E = epp[it.h], far = epp[nstep_last_row(H, W, it.h, nn)];
+        const int dfirst = days[(size_t)row0 * B + it.b];
+        const int dmine = days[(size_t)ring_wrap(row0 + min(tid, span - 1), H) * B + it.b];
+        it.m = has_ep && nn > 1 ? nstep_finish(rg, H, W, it.h, nn, E, far) : nn;
+        it.cnt = max(0, min(Lc, it.m - it.t0));
+        it.dA = dfirst - (W - 1);
+        const int ok = __all(tid >= it.cnt || dmine - dfirst == tid);
+        if ((tid & 63) == 0) flg[tid >> 6] = ok;
+        __syncthreads();
+        it.one = flg[0] & flg[1] & flg[2] & flg[3];
+        __syncthreads();
+    };
+    f4 mk[PPT];
+    float ac[PPT];
+    // the staging loads of a joint item, nothing waited (a lane past the item's pairs
+    // repeats the last pair's action load, as the n-step kernel does)
+    auto issue = [&](const Item& it) {
+        if (it.cnt == 0 || !it.one) return;
+        const int nd = W + it.cnt, P = R * nd;
+        const int hA = ring_wrap(it.h + it.t0, H);         // t0 < m < H
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) {
+            const int q = min(tid + k * 256, P - 1);
+            const int t = (int)fdiv((uint32_t)q, div_r), n = it.n0 + q - t * R;
+            ac[k] = actions[((size_t)ring_wrap(hA + t, H) * B + it.b) * N + n];
+            const int d = it.dA + t;
+            const bool in = tid + k * 256 < P && t < nd - 1 && d >= 0 && d < T;
+            mk[k] = buf_load4(rs_ser, in ? ((uint32_t)d * (uint32_t)N + (uint32_t)n) * 16u : 0xFFFFFFF0u);
+        }
+    };
+    Item c, n1 = {}, n2 = {};
+    bool v1 = (int)blockIdx.x + G < items, v2 = (int)blockIdx.x + 2 * G < items;
+    int i2 = (int)blockIdx.x + 2 * G;                      // the item n2 describes
+    raw((int)blockIdx.x, c);
+    if (v1) raw((int)blockIdx.x + G, n1);
+    if (v2) raw(i2, n2);
+    resolve(c);
+    if (v1) resolve(n1);
+    issue(c);
+    while (true) {
+        const int nE = min(Lc, L - c.t0);                  // the chunk's elements, cnt of them live
+        auto slot = [&](int t) {                           // element t of the chunk -> its output slot
+            return time_major ? (int64_t)(c.t0 + t) * S + c.j : (int64_t)c.j * L + c.t0 + t;
+        };
+        // elements [tb, te) of the chunk from the image, element t at a shift of t - tsh days
+        auto emit = [&](int tb, int te, int tsh) {
+            for (int q = tid; q < per / 4; q += 256) {
+                int off[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int e = 4 * q + k;
+                    off[k] = (int)__umul24(fdiv((uint32_t)e, div_wf), skip) + e;
+                }
+                for (int t = tb; t < te; ++t) {
+                    f4 v = f4{0.0f, 0.0f, 0.0f, 0.0f};
+                    if (t < c.cnt) {
+                        const float* p = img + (t - tsh) * F;
+                        v = f4{p[off[0]], p[off[1]], p[off[2]], p[off[3]]};
+                    }
+                    float* xo = x + (slot(t) * N + c.n0) * WF;
+                    buf_store4<NT>(make_rsrc(xo, (uint32_t)per * 4u), (uint32_t)q * 16u, v);
+                }
+            }
+            for (int q = tid; q < (te - tb) * R; q += 256) {           // a = actions[h0+t+W]: image day W + t
+                const int tq = (int)fdiv((uint32_t)q, div_r), nl = q - tq * R, t = tb + tq;
+                a_out[slot(t) * N + c.n0 + nl] = t < c.cnt ? img[((size_t)nl * D + W + t - tsh) * F + 4] : 0.0f;
+            }
+        };
+        if (c.n0 == 0) {
+            const int hr = ring_wrap(ring_wrap(c.h + W - 1, H) + min(c.t0, H), H);   // used where t0 < m only
+            for (int t = tid; t < nE; t += 256)
+                r_out[slot(t)] = t < c.cnt ? rewards[(size_t)ring_wrap(hr + t, H) * B + c.b] : 0.0f;
+            if (c.t0 == 0 && tid == 0) length[c.j] = c.m;
+        }
+        if (c.one) {
+            const int nd = W + c.cnt, P = c.cnt ? R * nd : 0;
+#pragma unroll
+            for (int k = 0; k < PPT; ++k) {
+                const int q = tid + k * 256;
+                if (q < P) {
+                    const int t = (int)fdiv((uint32_t)q, div_r), nl = q - t * R;
+                    const int d = c.dA + t;
+                    const bool in = t < nd - 1 && d >= 0 && d < T;
+                    float* dst = img + ((size_t)nl * D + t) * F;
+                    dst[0] = in ? mk[k].x : NAN;
+                    dst[1] = in ? mk[k].y : NAN;
+                    dst[2] = in ? mk[k].z : NAN;
+                    dst[3] = in ? mk[k].w : NAN;
+                    dst[4] = ac[k];
+                }
+            }
+            __syncthreads();
+            if (v1) issue(n1);                             // the next item's loads fly during the write-out
+            emit(0, nE, 0);
+        } else {
+            if (v1) issue(n1);
+            // days that skip: each live element staged on its own (W days and W + 1 action rows)
+            for (int t = 0; t < c.cnt; ++t) {
+                const int ht = ring_wrap(ring_wrap(c.h + c.t0, H) + t, H);
+                const int d0 = days[(size_t)ring_wrap(ht + W - 1, H) * B + c.b] - (W - 1);
+                for (int q = tid; q < R * (W + 1); q += 256) {
+                    const int p = (int)fdiv((uint32_t)q, div_r), nl = q - p * R, n = c.n0 + nl;
+                    const int d = d0 + p;
+                    const bool in = p < W && d >= 0 && d < T;
+                    f4 mv = f4{NAN, NAN, NAN, NAN};
+                    if (in) mv = *reinterpret_cast<const f4*>(series + ((size_t)d * N + n) * 4);
+                    float* dst = img + ((size_t)nl * D + p) * F;
+                    dst[0] = mv.x;
+                    dst[1] = mv.y;
+                    dst[2] = mv.z;
+                    dst[3] = mv.w;
+                    dst[4] = actions[((size_t)ring_wrap(ht + p, H) * B + c.b) * N + n];
+                }
+                __syncthreads();
+                emit(t, t + 1, t);
+                __syncthreads();
+            }
+            emit(c.cnt, nE, 0);                            // zeros: no LDS read
+        }
+        // index chain ahead: the item after next completes, the one behind it loads env / h0
+        Item n3 = {};
+        const int i3 = i2 + G;
+        const bool v3 = i3 < items;
+        if (v3) raw(i3, n3);
+        if (v2) resolve(n2);                               // its barriers also fence the image
+        else __syncthreads();
+        if (!v1) break;
+        c = n1;
+        n1 = n2; v1 = v2;
+        n2 = n3; v2 = v3; i2 = i3;
     }
 }
 

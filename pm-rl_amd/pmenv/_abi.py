@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("PMENV_LIB", os.path.join(HERE, "libpmenv.so"))
 PMENV_ABI_VERSION = 4   # 2: pmenv_window_written / pmenv_state_written; cfg default ret_mode GROSS
                         # 3: pmenv_step_host / pmenv_reset_host
                         # 4: pmenv_replay_gather_nstep
+                        #    (pmenv_replay_gather_seq added under 4: load() names a missing symbol)
 
 # enums (include/pmenv.h)
 REWARD_KINDS = {"log_returns": 0, "returns": 1, "sharpe_ratio": 2, "diff_sharpe": 3}
@@ -95,6 +96,9 @@ SIGNATURES = [
     ("pmenv_replay_gather_nstep", ctypes.c_int,
      [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, _F,
       _P, _P, _P, _P, _P, _P, _P]),
+    ("pmenv_replay_gather_seq", ctypes.c_int,
+     [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, _I32,
+      _P, _P, _P, _P, _P]),
     ("pmenv_rollout_gather", ctypes.c_int,
      [_P, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _P, _P]),
     ("pmenv_metrics", ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, ctypes.c_double, ctypes.c_double, _P, _P]),
@@ -125,7 +129,9 @@ def load():
     if ver() != PMENV_ABI_VERSION:
         raise ImportError(f"libpmenv ABI {ver()} != {PMENV_ABI_VERSION}: rebuild with `python pm-rl_amd/build.py`")
     for name, res, args in SIGNATURES:
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None:          # a library of the same ABI number built before the symbol was added
+            raise ImportError(f"{LIB_PATH} lacks {name}: rebuild with `python pm-rl_amd/build.py`")
         fn.restype = res
         fn.argtypes = args
     _lib = lib

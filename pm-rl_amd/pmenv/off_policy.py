@@ -13,6 +13,8 @@ and the evaluation metrics all on device.
     agent.update(epoch, step, s, a, r, s_) :92   update(s, a, r, s_)                   (caller's agent)
     add_experience's n_step fold (td3.py:85-106) replay.sample_nstep(batch_size, n)    (n_step > 1: HIP gather,
                                                  update(s, a, R, s_, discount)          folded at sample time)
+    x, a, r = data["x"], data["a"], data["r"]    replay.sample_sequences(batch_size, L) (seq_len > 0: HIP gather,
+      (agent/dreamer/dreamer.py:78)              update(x, a, r)                        [L, S, ..] time-major)
     metrics.write()                      :110    trajectory_metrics(...)               (HIP reductions)
 
 Every env trades the one HBM-resident series (pmenv.data.MarketSeries) from its own
@@ -27,15 +29,20 @@ from .replay import DeviceReplay, trajectory_metrics
 
 class OffPolicy:
     def __init__(self, env, series, capacity, act=None, update=None, batch_size=256, generator=None,
-                 n_step=1, gamma=0.997):
+                 n_step=1, gamma=0.997, seq_len=0):
         """env: a pmenv.TradingEnv over B envs; series: pmenv.data.MarketSeries [T, N, F-1];
         capacity: replay steps kept per env (buffer.py's ring); act(obs [B, N, W, F]) ->
         [B, N] weights; update(s, a, r, s_) -> anything (one agent update). n_step > 1
         (agent/td3/td3.py:85-106; gamma: config/dsac.py:30): update(s, a, R, s_, discount)
         with R the discounted sum of up to n_step rewards, s_ the state after the last of
-        them and discount [S] = gamma ** (rewards folded), the factor of the bootstrap term."""
+        them and discount [S] = gamma ** (rewards folded), the factor of the bootstrap term.
+        seq_len > 0 (agent/dreamer/dreamer.py:77-80; config/dreamer.py:5 BATCH_LEN):
+        update(x, a, r) with one batch of batch_size full-length sequences, time-major:
+        x [seq_len, S, N, W, F], a [seq_len, S, N], r [seq_len, S]."""
         if n_step < 1 or not 0.0 < gamma <= 1.0:
             raise ValueError("n_step must be >= 1 and gamma in (0, 1]")
+        if seq_len < 0 or (seq_len > 0 and n_step > 1):
+            raise ValueError("seq_len must be >= 0, and sequences do not combine with n_step > 1")
         cfg = env.cfg
         if series.num_assets != cfg.num_assets or series.channels != cfg.features - 1:
             raise ValueError("series must be [T, num_assets, features - 1]")
@@ -46,6 +53,7 @@ class OffPolicy:
         self.batch_size = batch_size
         self.generator = generator
         self.n_step, self.gamma = n_step, gamma
+        self.seq_len = seq_len
 
     def _random_action(self):
         """agent.act(s, is_random=True): uniform random portfolio weights (a simplex point)."""
@@ -80,6 +88,10 @@ class OffPolicy:
         """_update_off_policy (off_policy.py:88-94): `steps` sampled batches into update()."""
         out = []
         for _ in range(steps):
+            if self.seq_len > 0:
+                x, a, r, _ = self.replay.sample_sequences(self.batch_size, self.seq_len, self.generator)
+                out.append(self.update_fn(x, a, r) if self.update_fn is not None else None)
+                continue
             if self.n_step > 1:
                 s, a, r, s_, _, disc = self.replay.sample_nstep(self.batch_size, self.n_step, self.gamma,
                                                                 self.generator)

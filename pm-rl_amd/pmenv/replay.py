@@ -5,7 +5,8 @@ per recorded step it keeps only the day index of the window the agent acted on,
 the action and the reward; `sample` re-materialises the observation windows s, s'
 on device from the resident market series (pmenv.data.MarketSeries) with the last W
 actions as the weight channel, exactly as the reference rebuilds them from its
-dataset. `trajectory_metrics` restates util/eval.py:14-37 (Sharpe, Sortino, max
+dataset. `sample_nstep` folds n-step returns at sample time (agent/td3/td3.py:85-106) and
+`sample_sequences` serves sequences of consecutive steps (agent/dreamer/dreamer.py:77-80). `trajectory_metrics` restates util/eval.py:14-37 (Sharpe, Sortino, max
 drawdown, average turnover) per env on device.
 """
 import ctypes
@@ -56,6 +57,22 @@ def nstep_counts(row_episode, oldest, count, W, H, st, n):
     return np.minimum(run[st], n).astype(np.int32)
 
 
+def sequence_starts(row_episode, oldest, count, W, H, L):
+    """Offsets st (from the oldest recorded row) whose sequences of L elements are full
+    length, `nstep_counts(.., st, L) == L`: the one-step starts st .. st+L-1 are all valid,
+    i.e. st + L - 1 < count - W - 1 and rows st .. st+L-1+W share one episode (ids only grow
+    along the ring: the first and the last row decide). Returns a range when the ring holds
+    one episode (every start below count - W - L), else an int64 array."""
+    if L < 1:
+        raise ValueError("L must be >= 1")
+    span = max(count - W - L, 0)
+    ep = np.asarray(row_episode)
+    if span == 0 or ep[oldest] == ep[(oldest + count - 1) % H]:
+        return range(span)
+    chrono = np.roll(ep, -oldest)[:count]                 # rows oldest .. newest
+    return np.flatnonzero(chrono[:span] == chrono[W + L - 1:W + L - 1 + span])
+
+
 class DeviceReplay:
     def __init__(self, num_envs, num_assets, window, capacity, series, features=5):
         if capacity < window + 2:
@@ -76,6 +93,8 @@ class DeviceReplay:
         # the same ids on the device for the n-step gather, uploaded when a sample finds them stale
         self._row_ep_dev = torch.zeros(capacity, dtype=torch.int32, device=dev)
         self._row_ep_dirty = False
+        self._seq_starts = None       # as _starts, for full-length sequence starts (the key holds L)
+        self._seq_key = None
 
     def __len__(self):
         return self.count
@@ -180,6 +199,75 @@ class DeviceReplay:
     def sample_nstep(self, batch_size, n_step, gamma=0.997, generator=None):
         """`sample` with n-step returns (gamma: config/dsac.py:30)."""
         return self.gather_nstep(*self.indices(batch_size, generator), n_step, gamma)
+
+
+    def sequence_indices(self, batch_size, L, generator=None):
+        """Random (start, env) pairs whose sequences of L consecutive one-step samples are
+        full length: W + L recorded rows of one episode (`sequence_starts`). The generator
+        and device rules are those of `indices`."""
+        if L < 1:
+            raise ValueError("L must be >= 1")
+        span = self.count - self.W - L
+        if span < 1:
+            raise ValueError("no episode holds W + L recorded steps")
+        dev = self.days.device
+        gdev = generator.device if generator is not None else dev
+        oldest = (self.head - self.count) % self.H
+        first, last = int(self._row_ep[oldest]), int(self._row_ep[(oldest + self.count - 1) % self.H])
+        if first == last:                  # one episode in the ring: every start (no scan, no upload)
+            self._seq_key, self._seq_starts = None, None
+            st = torch.randint(0, span, (batch_size,), generator=generator, device=gdev)
+        else:
+            key = (oldest, self.count, first, last, L)
+            if self._seq_key != key:
+                ok = sequence_starts(self._row_ep, oldest, self.count, self.W, self.H, L)
+                self._seq_key, self._seq_starts = key, torch.as_tensor(np.asarray(ok), dtype=torch.int64).to(gdev)
+            if self._seq_starts.numel() == 0:
+                raise ValueError("no episode holds W + L recorded steps")
+            if self._seq_starts.device != torch.device(gdev):
+                self._seq_starts = self._seq_starts.to(gdev)
+            st = self._seq_starts[torch.randint(0, self._seq_starts.numel(), (batch_size,), generator=generator,
+                                                device=gdev)]
+        env = torch.randint(0, self.B, (batch_size,), generator=generator, device=gdev)
+        h0 = (oldest + st) % self.H
+        return h0.to(dev, torch.int32), env.to(dev, torch.int32)
+
+    def gather_sequences(self, h0, env, L, time_major=True):
+        """Sequences of L consecutive one-step samples from the given valid one-step starts:
+        (x, a, r, length). Element t of sequence j is `gather`'s (s, a, r) at start h0[j] + t.
+        time_major: x [L, S, N, W, F], a [L, S, N], r [L, S] (world_model.py:41-64 walks
+        [batch_len, batch_dim, ..]); else x [S, L, N, W, F], a [S, L, N], r [S, L]. length [S]
+        int32 is the number of valid elements — an episode boundary or the newest recorded
+        rows cut a sequence short (`nstep_counts` with n = L) — and the elements behind it
+        are zeros: length is the caller's mask."""
+        lib = _abi.load()
+        S, L = h0.numel(), int(L)
+        dev = self.days.device
+        if self._row_ep_dirty:
+            self._row_ep_dev.copy_(torch.from_numpy(self._row_ep.astype(np.int32)))
+            self._row_ep_dirty = False
+        lead = (L, S) if time_major else (S, L)
+        x = torch.empty(*lead, self.N, self.W, self.F, device=dev)
+        a = torch.empty(*lead, self.N, device=dev)
+        r = torch.empty(*lead, device=dev)
+        length = torch.empty(S, dtype=torch.int32, device=dev)
+        sb = self.series.bars
+        oldest = (self.head - self.count) % self.H
+        st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _abi.check(lib.pmenv_replay_gather_seq(_p(sb), sb.shape[0], self.N, self.F, self.W, _p(self.days),
+                                               _p(self.actions), _p(self.rewards), self.H, self.B,
+                                               _p(h0.contiguous()), _p(env.contiguous()), S, _p(self._row_ep_dev),
+                                               oldest, self.count, L, 1 if time_major else 0, _p(x), _p(a), _p(r),
+                                               _p(length), st), None, "pmenv_replay_gather_seq")
+        return x, a, r, length
+
+    def sample_sequences(self, batch_size, L, generator=None, time_major=True):
+        """A batch of full-length sequences for DreamerV3's world model:
+        agent/dreamer/dreamer.py:78 reads `x, a, r = data["x"], data["a"], data["r"]` — x the
+        observation windows, a the actions taken on them, r their rewards, [batch_len,
+        batch_dim, ..] with config/dreamer.py:4-5's BATCH_DIM = batch_size and BATCH_LEN = L.
+        Returns (x, a, r, length) as `gather_sequences`; every length is L."""
+        return self.gather_sequences(*self.sequence_indices(batch_size, L, generator), L, time_major)
 
 
 def trajectory_metrics(returns, values, weights, risk_free_rate=RISK_FREE_RATE, periods=252):

@@ -898,6 +898,13 @@ bool gae(const float* rewards, const float* values, const uint8_t* dones, float*
     return true;
 }
 
+// sequence gather: PMENV_SEQ_NT = 0 / 2 / 16 (plain, nt, sc1 window stores), PMENV_SEQ_LC =
+// elements per chunk
+void replay_seq_knobs(int* policy, int* chunk) {
+    if (knob("PMENV_SEQ_NT")) *policy = knob_int("PMENV_SEQ_NT", -1);
+    if (knob("PMENV_SEQ_LC")) *chunk = knob_int("PMENV_SEQ_LC", 0);
+}
+
 // replay gather: PMENV_REPLAY_LDS (the per-element staging kernel), PMENV_REPLAY_NT=0
 // (default-policy stores), PMENV_REPLAY_PERSIST=0 (one workgroup per sample),
 // PMENV_REPLAY_TPB=512, PMENV_REPLAY_GRID=G

@@ -285,7 +285,59 @@ def main():
             gather_n(n)
             res.append(row(f"replay_gather_nstep_n{n}", us, alg, S=S, N=N, W=W, B=B, n=n, ratio=round(us / one, 4),
                            mean_steps=round(float(stp.float().mean()), 2)))
-        del rb, s_, s2
+        # sequence gather on the same ring beside the composition it replaces — the one-step
+        # gather over the S*L pre-expanded indices (h0 + t, env), time-major, built outside the
+        # timed region — same process, alternating: Dreamer's own batch (16 x 64) and 8,192
+        # windows (128 x 64, as many as config 3's one-step s). Then the tools build's knobs:
+        # the window stores' cache policy and the elements per chunk
+        xq = torch.empty_like(s_)
+        for Sq, L in ((16, 64), (128, 64)):
+            Wn = Sq * L
+            h0q, eq = rb.sequence_indices(Sq, L, generator=torch.Generator().manual_seed(3))
+            tq = torch.arange(L, device=dev, dtype=torch.int32)[:, None]
+            h0e = ((h0q[None, :] + tq) % H).reshape(-1).contiguous()
+            ee = eq[None, :].expand(L, Sq).reshape(-1).contiguous()
+            aq, rq = torch.empty(L, Sq, N, device=dev), torch.empty(L, Sq, device=dev)
+            lq = torch.empty(Sq, dtype=torch.int32, device=dev)
+
+            def composed():
+                ck(lib.pmenv_replay_gather(P(sb), sb.shape[0], N, 5, W, P(rb.days), P(rb.actions), P(rb.rewards), H,
+                                           B, P(h0e), P(ee), Wn, P(s_), P(s2), P(ao), P(ro), st), "gather")
+
+            def seq():
+                ck(lib.pmenv_replay_gather_seq(P(sb), sb.shape[0], N, 5, W, P(rb.days), P(rb.actions), P(rb.rewards),
+                                               H, B, P(h0q), P(eq), Sq, P(rb._row_ep_dev), oldest, rb.count, L, 1,
+                                               P(xq), P(aq), P(rq), P(lq), st), "gather_seq")
+            knobs = ("PMENV_SEQ_NT", "PMENV_SEQ_LC")
+            for k in knobs:
+                os.environ.pop(k, None)
+            composed()
+            seq()
+            same = bool(torch.equal(xq.view(-1)[:Wn * N * W * 5].view(torch.int32),
+                                    s_.view(-1)[:Wn * N * W * 5].view(torch.int32)) and
+                        torch.equal(aq.view(-1), ao.view(-1)[:Wn * N]) and torch.equal(rq.view(-1), ro[:Wn]) and
+                        bool((lq == L).all()))
+            tc, ts = [], []
+            for _ in range(5):
+                tc.append(timeit(composed, a.reps))
+                ts.append(timeit(seq, a.reps))
+            comp, us = statistics.median(tc), statistics.median(ts)
+            alg_c = Wn * (2 * N * W * 5 * 4 + N * 4 + 4)
+            alg_s = Wn * (N * W * 5 * 4 + N * 4 + 4)
+            res.append(row(f"replay_gather_composed_S{Sq}_L{L}", comp, alg_c, S=Sq, L=L, N=N, W=W, B=B,
+                           spread=round((max(tc) - min(tc)) / comp, 4)))
+            res.append(row(f"replay_gather_seq_S{Sq}_L{L}", us, alg_s, S=Sq, L=L, N=N, W=W, B=B,
+                           ratio=round(us / comp, 4), spread=round((max(ts) - min(ts)) / us, 4), same_bits=same,
+                           frac_write_stream=round(alg_s / us / 1e6 / 4.24, 3)))
+            if "libpmenv_ab" in os.path.basename(_abi.LIB_PATH):
+                for k, vals in (("PMENV_SEQ_NT", (0, 2, 16)), ("PMENV_SEQ_LC", (1, 2, 4, 8, 16, 32))):
+                    for v in vals:
+                        os.environ[k] = str(v)
+                        us_k = statistics.median([timeit(seq, a.reps) for _ in range(3)])
+                        res.append(row(f"replay_gather_seq_S{Sq}_L{L}_{k[6:].lower()}{v}", us_k, alg_s, S=Sq, L=L,
+                                       ratio=round(us_k / comp, 4)))
+                    os.environ.pop(k, None)
+        del rb, s_, s2, xq
         for T, B in ((252, 65536), (252, 4096)):
             rets = 0.001 * torch.randn(T, B, device=dev, dtype=torch.float64, generator=g)
             vals = torch.cumprod(torch.cat([torch.ones(1, B, device=dev, dtype=torch.float64), 1 + rets]), 0)
