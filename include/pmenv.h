@@ -439,6 +439,67 @@ int pmenv_replay_gather_seq(const float* series, int32_t T, int32_t N, int32_t F
                             int32_t oldest, int32_t count, int32_t L, int32_t time_major,
                             float* x, float* a_out, float* r_out, int32_t* length, hipStream_t stream);
 
+/* ---- prioritized sampling over the same ring. agent/td3/td3.py:39 builds
+ * PrioritizedReplayBuffer(buffer_size, alpha, beta, beta_incr), :118 reads `samples, idxs,
+ * weights = replay_buffer.sample(batch_size)`, :126,143 weight the critic loss and :144
+ * calls update_priorities(idxs, td_error). The module td3.py:12 imports is not in the
+ * reference tree, so parity is unpinned; the definitions are those of Schaul et al. 2016,
+ * "Prioritized Experience Replay", proportional variant: P(j) = p_j^alpha / sum_k p_k^alpha,
+ * w_j = (N P(j))^-beta / max_k w_k, p_j = |td_j| + eps, new transitions enter at the largest
+ * priority seen.
+ *
+ * The tree is a radix-64 sum tree over `leaves` = H * B leaves, 1 <= leaves < 2^31. Leaf
+ * l = h * B + b is the one-step sample that starts at ring row h of env b; it is an f32 and
+ * holds p^alpha, and it is 0 exactly when (h, b) is not a valid one-step start. Level 0 is
+ * the leaves, n_0 = leaves; level k >= 1 has n_k = ceil(n_{k-1} / 64) f64 nodes, node i the
+ * sum of entries [64 i, 64 i + 64) of level k - 1 that exist; the levels end with the first
+ * k >= 1 that has n_k <= 64 (so there is always a level 1). One caller-owned device buffer
+ * of pmenv_prio_tree_bytes(leaves) bytes, 8-byte aligned (PMENV_ERR_ALIGN), holds
+ *
+ *     [0, 64)                        header: f32 at byte 0 = the running maximum leaf value
+ *     [64, 64 + 4 * pad(n_0))        the leaves (f32)
+ *     then for k = 1, 2, ..          level k: 8 * pad(n_k) bytes (f64)
+ *
+ * with pad(n) = 64 * ceil(n / 64): every level is padded with zeros, which the calls never
+ * change. Every call validates its arguments (PMENV_ERR_ARG), enqueues a linear chain of
+ * launches on `stream`, never allocates, frees or synchronises, may be captured in a
+ * hipGraph, and is deterministic: a touched node is recomputed from its 64 children in a
+ * fixed order, there are no floating-point atomics, and the same inputs give the same bits
+ * whatever the dispatch order. ---- */
+size_t pmenv_prio_tree_bytes(int64_t leaves); /* 0 when leaves is outside [1, 2^31) */
+/* Every leaf and node 0, the maximum 1. */
+int pmenv_prio_init(void* tree, int64_t leaves, hipStream_t stream);
+/* Leaves [close_first, close_first + n) become 0 and leaves [open_first, open_first + n)
+ * the current maximum; every ancestor is refreshed. A negative first = that range is
+ * absent. The ranges must lie inside the leaves and must not overlap. The replay calls it
+ * once per recorded step with n = B: the ring row just overwritten closes and the row whose
+ * window became complete opens. */
+int pmenv_prio_fill(void* tree, int64_t leaves, int64_t close_first, int64_t open_first, int64_t n,
+                    hipStream_t stream);
+/* S samples (td3.py:118). Sample j takes the target u[j] * total, u[j] in [0, 1) (f64),
+ * total = the sum of the top level in the order the descent scans it (a 64-lane prefix
+ * scan). At each node the first child with a positive value whose inclusive prefix exceeds
+ * the residual is chosen and its exclusive prefix subtracted; a child of value 0 is never
+ * chosen; if rounding leaves the residual at or above the node's sum, the last child with a
+ * positive value is taken. leaf_out [S] = the leaf, h0_out = leaf / B, env_out = leaf % B
+ * (ready for the gathers above), weight_out [S] = (leaf_j / min_k leaf_k)^-beta over the
+ * batch's leaf values, in f64, rounded once. That is the paper's (N P(j))^-beta / max_k w_k:
+ * N and total cancel under the batch-max normalisation, and the largest weight is exactly
+ * 1. An empty tree gives leaf 0 and weight 0. beta >= 0. */
+int pmenv_prio_sample(const void* tree, int64_t leaves, int32_t B, const double* u, int32_t S, float beta,
+                      int32_t* leaf_out, int32_t* h0_out, int32_t* env_out, float* weight_out,
+                      hipStream_t stream);
+/* update_priorities (td3.py:144): leaf[j] takes max((|td[j]| + eps)^alpha, FLT_MIN),
+ * computed in f64, rounded once to f32 and capped at FLT_MAX; a non-finite td gives the
+ * maximum the header held when the call began. A leaf that is 0 stays 0 (its row was
+ * overwritten or closed since it was sampled) and its ancestors keep their bits. Where
+ * leaf[] repeats an index the largest new value wins, whatever the order; the old value is
+ * no candidate. The header's maximum becomes max(old, every finite new value). Every
+ * ancestor of a touched leaf is refreshed, level by level. Indices outside [0, leaves) are
+ * skipped. alpha >= 0, eps >= 0. */
+int pmenv_prio_update(void* tree, int64_t leaves, const int32_t* leaf, const float* td, int32_t S,
+                      float alpha, float eps, hipStream_t stream);
+
 /* The compact on-policy rollout (replay/rollout_buffer.py:43-57 stores s per step;
  * here the windows are re-materialised instead): for each of the S
  * samples (t_idx[j], env[j]) writes s[j] = env b's window after t updates, [N, W, F]:

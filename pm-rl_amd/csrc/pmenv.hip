@@ -26,6 +26,7 @@
 #include "data.h"
 #include "handle.h"
 #include "launch.h"
+#include "prio.h"
 #include "replay.h"
 #include "rollout.h"
 #include "trainer.h"
@@ -1539,6 +1540,80 @@ int pmenv_replay_gather_seq(const float* series, int32_t T, int32_t N, int32_t F
         replay_seq_kernel<<<(unsigned)blocks, 256, 0, stream>>>(series, T, N, F, W, days, actions, rewards, H, B, h0,
                                                                env, S, rg, time_major, x, a_out, r_out, length);
     }
+    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
+// ---- the priority tree (prio.h): stateless, every call enqueues a linear chain on `stream`
+static bool prio_tree_ok(const void* tree, int64_t leaves) {
+    return tree && leaves >= 1 && leaves < ((int64_t)1 << 31);
+}
+
+size_t pmenv_prio_tree_bytes(int64_t leaves) {
+    if (leaves < 1 || leaves >= ((int64_t)1 << 31)) return 0;
+    return prio_layout(leaves).bytes;
+}
+
+int pmenv_prio_init(void* tree, int64_t leaves, hipStream_t stream) {
+    if (!prio_tree_ok(tree, leaves)) return PMENV_ERR_ARG;
+    if ((uintptr_t)tree & 7u) return PMENV_ERR_ALIGN;
+    const size_t words = prio_layout(leaves).bytes / 8;
+    const size_t blocks = (words + 255) / 256;
+    prio_init_kernel<<<(unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, stream>>>((unsigned long long*)tree, words);
+    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
+int pmenv_prio_fill(void* tree, int64_t leaves, int64_t close_first, int64_t open_first, int64_t n,
+                    hipStream_t stream) {
+    if (!prio_tree_ok(tree, leaves) || n < 0) return PMENV_ERR_ARG;
+    if ((uintptr_t)tree & 7u) return PMENV_ERR_ALIGN;
+    const int64_t c0 = close_first < 0 ? -1 : close_first, o0 = open_first < 0 ? -1 : open_first;
+    if ((c0 >= 0 && c0 + n > leaves) || (o0 >= 0 && o0 + n > leaves)) return PMENV_ERR_ARG;
+    if (c0 >= 0 && o0 >= 0 && c0 < o0 + n && o0 < c0 + n && n > 0) return PMENV_ERR_ARG;   // the ranges overlap
+    if (n == 0 || (c0 < 0 && o0 < 0)) return PMENV_OK;
+    const PrioTree t = prio_layout(leaves);
+    char* base = (char*)tree;
+    for (int k = 1; k <= t.levels; ++k) {
+        const int sh = 6 * k;
+        const int64_t cc = c0 < 0 ? 0 : ((c0 + n - 1) >> sh) - (c0 >> sh) + 1;
+        const int64_t oc = o0 < 0 ? 0 : ((o0 + n - 1) >> sh) - (o0 >> sh) + 1;
+        prio_fill_kernel<<<(unsigned)((cc + oc + 3) / 4), 256, 0, stream>>>(
+            (const float*)base, (float*)(base + t.off[0]), (const double*)(base + t.off[k - 1]),
+            (double*)(base + t.off[k]), leaves, c0, o0, n, sh);
+    }
+    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
+int pmenv_prio_sample(const void* tree, int64_t leaves, int32_t B, const double* u, int32_t S, float beta,
+                      int32_t* leaf_out, int32_t* h0_out, int32_t* env_out, float* weight_out, hipStream_t stream) {
+    if (!prio_tree_ok(tree, leaves) || !u || !leaf_out || !h0_out || !env_out || !weight_out || B < 1 || S < 1 ||
+        !(beta >= 0.0f) || !std::isfinite(beta))
+        return PMENV_ERR_ARG;
+    if ((uintptr_t)tree & 7u) return PMENV_ERR_ALIGN;
+    prio_sample_kernel<<<(unsigned)((S + 3) / 4), 256, 0, stream>>>((const char*)tree, prio_layout(leaves), B, u, S,
+                                                                   leaf_out, h0_out, env_out, weight_out);
+    const int wblocks = (S + 1023) / 1024;
+    prio_weight_kernel<<<(unsigned)(wblocks < 16 ? wblocks : 16), 1024, 0, stream>>>(
+        (const float*)((const char*)tree + kPrioHeaderBytes), leaf_out, weight_out, S, (double)beta);
+    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
+int pmenv_prio_update(void* tree, int64_t leaves, const int32_t* leaf, const float* td, int32_t S, float alpha,
+                      float eps, hipStream_t stream) {
+    if (!prio_tree_ok(tree, leaves) || !leaf || !td || S < 1 || !(alpha >= 0.0f) || !std::isfinite(alpha) ||
+        !(eps >= 0.0f) || !std::isfinite(eps))
+        return PMENV_ERR_ARG;
+    if ((uintptr_t)tree & 7u) return PMENV_ERR_ALIGN;
+    const PrioTree t = prio_layout(leaves);
+    char* base = (char*)tree;
+    uint32_t* bits = (uint32_t*)(base + t.off[0]);
+    const unsigned tb = (unsigned)((S + 255) / 256), wb = (unsigned)((S + 3) / 4);
+    prio_mark_kernel<<<tb, 256, 0, stream>>>(bits, leaves, leaf, S);
+    prio_apply_kernel<<<tb, 256, 0, stream>>>((const float*)base, bits, leaves, leaf, td, S, (double)alpha,
+                                             (double)eps);
+    for (int k = 1; k <= t.levels; ++k)
+        prio_refresh_kernel<<<wb, 256, 0, stream>>>((uint32_t*)base, (const float*)(base + t.off[0]),
+                                                   (const double*)(base + t.off[k - 1]), (double*)(base + t.off[k]),
+                                                   leaves, leaf, td, S, (double)alpha, (double)eps, 6 * k);
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
 

@@ -16,7 +16,8 @@ LIB_PATH = os.environ.get("PMENV_LIB", os.path.join(HERE, "libpmenv.so"))
 PMENV_ABI_VERSION = 4   # 2: pmenv_window_written / pmenv_state_written; cfg default ret_mode GROSS
                         # 3: pmenv_step_host / pmenv_reset_host
                         # 4: pmenv_replay_gather_nstep
-                        #    (pmenv_replay_gather_seq added under 4: load() names a missing symbol)
+                        #    (pmenv_replay_gather_seq and pmenv_prio_* added under 4: load() names a
+                        #    missing symbol)
 
 # enums (include/pmenv.h)
 REWARD_KINDS = {"log_returns": 0, "returns": 1, "sharpe_ratio": 2, "diff_sharpe": 3}
@@ -99,6 +100,11 @@ SIGNATURES = [
     ("pmenv_replay_gather_seq", ctypes.c_int,
      [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, _I32,
       _P, _P, _P, _P, _P]),
+    ("pmenv_prio_tree_bytes", _SZ, [_I64]),
+    ("pmenv_prio_init", ctypes.c_int, [_P, _I64, _P]),
+    ("pmenv_prio_fill", ctypes.c_int, [_P, _I64, _I64, _I64, _I64, _P]),
+    ("pmenv_prio_sample", ctypes.c_int, [_P, _I64, _I32, _P, _I32, _F, _P, _P, _P, _P, _P]),
+    ("pmenv_prio_update", ctypes.c_int, [_P, _I64, _P, _P, _I32, _F, _F, _P]),
     ("pmenv_rollout_gather", ctypes.c_int,
      [_P, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _P, _P]),
     ("pmenv_metrics", ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, ctypes.c_double, ctypes.c_double, _P, _P]),

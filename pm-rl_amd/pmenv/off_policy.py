@@ -15,6 +15,9 @@ and the evaluation metrics all on device.
                                                  update(s, a, R, s_, discount)          folded at sample time)
     x, a, r = data["x"], data["a"], data["r"]    replay.sample_sequences(batch_size, L) (seq_len > 0: HIP gather,
       (agent/dreamer/dreamer.py:78)              update(x, a, r)                        [L, S, ..] time-major)
+    samples, idxs, weights = replay_buffer.sample(..) replay.sample_prioritized(batch_size)  (prioritized: HIP sum tree,
+    update_priorities(idxs, td_error)            td = update(s, a, r, s_, weights);     agent/td3/td3.py:118-144)
+      (agent/td3/td3.py:118,144)                 replay.update_priorities(leaf, td)
     metrics.write()                      :110    trajectory_metrics(...)               (HIP reductions)
 
 Every env trades the one HBM-resident series (pmenv.data.MarketSeries) from its own
@@ -29,7 +32,7 @@ from .replay import DeviceReplay, trajectory_metrics
 
 class OffPolicy:
     def __init__(self, env, series, capacity, act=None, update=None, batch_size=256, generator=None,
-                 n_step=1, gamma=0.997, seq_len=0):
+                 n_step=1, gamma=0.997, seq_len=0, prioritized=False, alpha=0.6, beta=0.4, beta_increment=0.0):
         """env: a pmenv.TradingEnv over B envs; series: pmenv.data.MarketSeries [T, N, F-1];
         capacity: replay steps kept per env (buffer.py's ring); act(obs [B, N, W, F]) ->
         [B, N] weights; update(s, a, r, s_) -> anything (one agent update). n_step > 1
@@ -38,22 +41,30 @@ class OffPolicy:
         them and discount [S] = gamma ** (rewards folded), the factor of the bootstrap term.
         seq_len > 0 (agent/dreamer/dreamer.py:77-80; config/dreamer.py:5 BATCH_LEN):
         update(x, a, r) with one batch of batch_size full-length sequences, time-major:
-        x [seq_len, S, N, W, F], a [seq_len, S, N], r [seq_len, S]."""
+        x [seq_len, S, N, W, F], a [seq_len, S, N], r [seq_len, S].
+        prioritized (agent/td3/td3.py:39,118-144): batches are drawn by priority and
+        update(s, a, r, s_, weights) -> td_error [S] — with n_step > 1 update(s, a, R, s_,
+        discount, weights) — whose result goes to replay.update_priorities; weights [S] are
+        the importance weights of the critic loss (:126,143). Not with seq_len > 0."""
         if n_step < 1 or not 0.0 < gamma <= 1.0:
             raise ValueError("n_step must be >= 1 and gamma in (0, 1]")
         if seq_len < 0 or (seq_len > 0 and n_step > 1):
             raise ValueError("seq_len must be >= 0, and sequences do not combine with n_step > 1")
+        if prioritized and seq_len > 0:
+            raise ValueError("sequence samples stay uniform: prioritized does not combine with seq_len > 0")
         cfg = env.cfg
         if series.num_assets != cfg.num_assets or series.channels != cfg.features - 1:
             raise ValueError("series must be [T, num_assets, features - 1]")
         self.env, self.series = env, series
         self.B, self.N, self.W = cfg.num_envs, cfg.num_assets, cfg.window
-        self.replay = DeviceReplay(self.B, self.N, self.W, capacity, series, cfg.features)
+        self.replay = DeviceReplay(self.B, self.N, self.W, capacity, series, cfg.features, prioritized=prioritized,
+                                   alpha=alpha, beta=beta, beta_increment=beta_increment)
         self.act_fn, self.update_fn = act, update
         self.batch_size = batch_size
         self.generator = generator
         self.n_step, self.gamma = n_step, gamma
         self.seq_len = seq_len
+        self.prioritized = prioritized
 
     def _random_action(self):
         """agent.act(s, is_random=True): uniform random portfolio weights (a simplex point)."""
@@ -91,6 +102,19 @@ class OffPolicy:
             if self.seq_len > 0:
                 x, a, r, _ = self.replay.sample_sequences(self.batch_size, self.seq_len, self.generator)
                 out.append(self.update_fn(x, a, r) if self.update_fn is not None else None)
+                continue
+            if self.prioritized:
+                if self.n_step > 1:
+                    s, a, r, s_, _, disc, leaf, w = self.replay.sample_nstep_prioritized(
+                        self.batch_size, self.n_step, self.gamma, self.generator)
+                    args = (s, a, r, s_, disc, w)
+                else:
+                    s, a, r, s_, leaf, w = self.replay.sample_prioritized(self.batch_size, self.generator)
+                    args = (s, a, r, s_, w)
+                td = self.update_fn(*args) if self.update_fn is not None else None
+                if td is not None:
+                    self.replay.update_priorities(leaf, td)
+                out.append(td)
                 continue
             if self.n_step > 1:
                 s, a, r, s_, _, disc = self.replay.sample_nstep(self.batch_size, self.n_step, self.gamma,

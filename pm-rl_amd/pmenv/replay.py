@@ -6,7 +6,10 @@ the action and the reward; `sample` re-materialises the observation windows s, s
 on device from the resident market series (pmenv.data.MarketSeries) with the last W
 actions as the weight channel, exactly as the reference rebuilds them from its
 dataset. `sample_nstep` folds n-step returns at sample time (agent/td3/td3.py:85-106) and
-`sample_sequences` serves sequences of consecutive steps (agent/dreamer/dreamer.py:77-80). `trajectory_metrics` restates util/eval.py:14-37 (Sharpe, Sortino, max
+`sample_sequences` serves sequences of consecutive steps (agent/dreamer/dreamer.py:77-80).
+`prioritized=True` keeps a resident sum tree over the one-step starts (td3.py:39,118,144;
+Schaul et al. 2016, proportional variant): `sample_prioritized`, `update_priorities`.
+`trajectory_metrics` restates util/eval.py:14-37 (Sharpe, Sortino, max
 drawdown, average turnover) per env on device.
 """
 import ctypes
@@ -73,10 +76,98 @@ def sequence_starts(row_episode, oldest, count, W, H, L):
     return np.flatnonzero(chrono[:span] == chrono[W + L - 1:W + L - 1 + span])
 
 
+def prio_row_events(row_episode, head, count, episode, W, H):
+    """The leaves one `add` changes, decided on the host from the ring state BEFORE the add
+    (row ids, head, count) — no torch, no device: (close_row or None, open_row or None).
+    close_row is the ring row about to be overwritten (a full ring loses its oldest start).
+    open_row is the start at offset count' - W - 2 of the ring after the add, the only start
+    the new row can complete, and only when its rows st .. st + W share one episode. Those
+    rows were all recorded before this add (a start's window ends one row short of the
+    newest, `valid_starts`), so `episode`, the id of the row being added, decides nothing;
+    it is part of the state the caller hands over. After every add the open rows are
+    exactly {(oldest + st) % H : st in valid_starts(..)}."""
+    close_row = head if count == H else None
+    count2 = min(count + 1, H)
+    oldest2 = (head + 1 - count2) % H
+    st = count2 - W - 2
+    open_row = None
+    if st >= 0:
+        first, last = (oldest2 + st) % H, (oldest2 + st + W) % H
+        if row_episode[first] == row_episode[last]:
+            open_row = first
+    return close_row, open_row
+
+
+def prio_layout(leaves):
+    """The byte layout of the priority tree (include/pmenv.h): {header: 0, levels: [(byte
+    offset, entries, numpy dtype), ..], bytes}; level 0 is the f32 leaves, the others f64,
+    each padded with zeros to a multiple of 64 entries."""
+    pad = lambda n: (n + 63) // 64 * 64  # noqa: E731
+    levels, off, n = [(64, leaves, np.float32)], 64 + 4 * pad(leaves), leaves
+    while True:
+        n = (n + 63) // 64
+        levels.append((off, n, np.float64))
+        off += 8 * pad(n)
+        if n <= 64:
+            return dict(header=0, levels=levels, bytes=off)
+
+
+def _stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def prio_tree(leaves, device):
+    """A zeroed tree buffer for `leaves` leaves with the maximum at 1 (pmenv_prio_init)."""
+    lib = _abi.load()
+    nbytes = lib.pmenv_prio_tree_bytes(leaves)
+    if nbytes == 0:
+        raise ValueError("leaves must be in [1, 2^31)")
+    tree = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    _abi.check(lib.pmenv_prio_init(_p(tree), leaves, _stream(tree.device)), None, "pmenv_prio_init")
+    return tree
+
+
+def prio_fill(tree, leaves, close_first, open_first, n):
+    """pmenv_prio_fill: n leaves from close_first become 0, n from open_first the maximum
+    (None: that range is absent)."""
+    _abi.check(_abi.load().pmenv_prio_fill(_p(tree), leaves, -1 if close_first is None else close_first,
+                                           -1 if open_first is None else open_first, n, _stream(tree.device)),
+               None, "pmenv_prio_fill")
+
+
+def prio_sample(tree, leaves, B, u, beta, out=None):
+    """pmenv_prio_sample for targets u [S] f64 in [0, 1): (leaf, h0, env int32, weights f32).
+    out: the four preallocated outputs (a captured graph's buffers)."""
+    S, dev = u.numel(), tree.device
+    if out is None:
+        out = tuple(torch.empty(S, dtype=torch.int32, device=dev) for _ in range(3)) + (
+            torch.empty(S, dtype=torch.float32, device=dev),)
+    leaf, h0, env, w = out
+    _abi.check(_abi.load().pmenv_prio_sample(_p(tree), leaves, B, _p(u), S, float(beta), _p(leaf), _p(h0), _p(env),
+                                             _p(w), _stream(dev)), None, "pmenv_prio_sample")
+    return leaf, h0, env, w
+
+
+def prio_update(tree, leaves, leaf, td, alpha, eps):
+    """pmenv_prio_update: leaf int32 [S], td f32 [S]."""
+    _abi.check(_abi.load().pmenv_prio_update(_p(tree), leaves, _p(leaf), _p(td), leaf.numel(), float(alpha),
+                                             float(eps), _stream(tree.device)), None, "pmenv_prio_update")
+
+
 class DeviceReplay:
-    def __init__(self, num_envs, num_assets, window, capacity, series, features=5):
+    def __init__(self, num_envs, num_assets, window, capacity, series, features=5, prioritized=False, alpha=0.6,
+                 beta=0.4, beta_increment=0.0, eps=1e-6):
+        """prioritized (agent/td3/td3.py:39 PrioritizedReplayBuffer(buffer_size, alpha, beta,
+        beta_incr)): keep a priority tree over the H * B one-step starts, current after every
+        `add`; `sample_prioritized` / `sample_nstep_prioritized` draw from it and
+        `update_priorities` feeds the TD errors back. Sequence samples stay uniform: a
+        sequence start has another validity set than a one-step start."""
         if capacity < window + 2:
             raise ValueError("capacity must hold at least window + 2 steps")
+        if prioritized and (alpha < 0 or not 0.0 <= beta <= 1.0 or beta_increment < 0 or eps < 0):
+            raise ValueError("alpha, beta_increment, eps must be >= 0 and beta in [0, 1]")
+        if prioritized and capacity * num_envs >= 2 ** 31:
+            raise ValueError("a prioritized replay holds fewer than 2^31 transitions")
         self.B, self.N, self.W, self.F, self.H = num_envs, num_assets, window, features, capacity
         self.series = series
         dev = series.device
@@ -95,6 +186,11 @@ class DeviceReplay:
         self._row_ep_dirty = False
         self._seq_starts = None       # as _starts, for full-length sequence starts (the key holds L)
         self._seq_key = None
+        self.prioritized = bool(prioritized)
+        self.alpha, self.beta, self.beta_increment, self.eps = alpha, beta, beta_increment, eps
+        self._leaves = capacity * num_envs
+        self._row_open = np.zeros(capacity, dtype=bool)   # ring rows whose leaves are open (valid starts), kept by add
+        self.tree = prio_tree(self._leaves, dev) if prioritized else None
 
     def __len__(self):
         return self.count
@@ -107,6 +203,8 @@ class DeviceReplay:
     def add(self, day, action, reward):
         """buffer.py:23-37: one recorded step for every env."""
         h = self.head
+        if self.prioritized:              # from the state before the add
+            close_row, open_row = prio_row_events(self._row_ep, h, self.count, self.episode, self.W, self.H)
         self.days[h].copy_(torch.as_tensor(day).reshape(self.B))
         self.actions[h].copy_(torch.as_tensor(action).reshape(self.B, self.N))
         self.rewards[h].copy_(torch.as_tensor(reward).reshape(self.B))
@@ -114,6 +212,14 @@ class DeviceReplay:
         self._row_ep[h] = self.episode
         self.head = (h + 1) % self.H
         self.count = min(self.count + 1, self.H)
+        if self.prioritized:
+            if close_row is not None:     # the host's copy of which rows are open: no device read to count them
+                self._row_open[close_row] = False
+            if open_row is not None:
+                self._row_open[open_row] = True
+            if close_row is not None or open_row is not None:
+                prio_fill(self.tree, self._leaves, None if close_row is None else close_row * self.B,
+                          None if open_row is None else open_row * self.B, self.B)
 
     def indices(self, batch_size, generator=None):
         """Random (start, env) pairs with W+1 consecutive recorded steps of one episode
@@ -199,6 +305,54 @@ class DeviceReplay:
     def sample_nstep(self, batch_size, n_step, gamma=0.997, generator=None):
         """`sample` with n-step returns (gamma: config/dsac.py:30)."""
         return self.gather_nstep(*self.indices(batch_size, generator), n_step, gamma)
+
+    def prioritized_indices(self, batch_size, generator=None, u=None):
+        """`samples, idxs, weights = replay_buffer.sample(batch_size)` of agent/td3/td3.py:118,
+        the index part: (h0, env, leaf, weights). Sample j descends the priority tree to the
+        target u[j] * total; u [S] in [0, 1) defaults to the stratified draw (arange(S) +
+        rand(S)) / S of Schaul et al. 2016, with `indices`' generator and device rules; an
+        explicit u makes the draw exact. leaf = h0 * B + env is what `update_priorities` takes
+        back; weights [S] f32 = (N P(j))^-beta / max_k w_k with the current beta, which then
+        advances by beta_increment, capped at 1 (td3.py:39 beta_incr)."""
+        if not self.prioritized:
+            raise ValueError("the replay was built with prioritized=False")
+        if self.count - self.W - 1 < 1:
+            raise ValueError("not enough recorded steps to sample a window")
+        if not self._row_open.any():
+            raise ValueError("no episode holds W + 1 recorded steps")
+        dev = self.days.device
+        if u is None:
+            gdev = generator.device if generator is not None else dev
+            u = (torch.arange(batch_size, dtype=torch.float64, device=gdev) +
+                 torch.rand(batch_size, dtype=torch.float64, generator=generator, device=gdev)) / batch_size
+        u = torch.as_tensor(u, dtype=torch.float64).to(dev).reshape(batch_size).contiguous()
+        beta = self.beta
+        self.beta = min(1.0, beta + self.beta_increment)
+        leaf, h0, env, w = prio_sample(self.tree, self._leaves, self.B, u, beta)
+        return h0, env, leaf, w
+
+    def sample_prioritized(self, batch_size, generator=None, u=None):
+        """`sample` drawn by priority: (s, a, r, s_next, leaf, weights)."""
+        h0, env, leaf, w = self.prioritized_indices(batch_size, generator, u)
+        return self.gather(h0, env) + (leaf, w)
+
+    def sample_nstep_prioritized(self, batch_size, n_step, gamma=0.997, generator=None, u=None):
+        """`sample_nstep` drawn by priority: (s, a, R, s_next, steps, discount, leaf, weights)."""
+        h0, env, leaf, w = self.prioritized_indices(batch_size, generator, u)
+        return self.gather_nstep(h0, env, n_step, gamma) + (leaf, w)
+
+    def update_priorities(self, leaf, td_error):
+        """replay_buffer.update_priorities(idxs, td_error) of agent/td3/td3.py:144: leaf j takes
+        (|td_error[j]| + eps)^alpha. A leaf whose row was overwritten or closed since it was
+        sampled stays closed; of repeated leaves the largest value wins."""
+        if not self.prioritized:
+            raise ValueError("the replay was built with prioritized=False")
+        dev = self.days.device
+        leaf = torch.as_tensor(leaf).to(dev, torch.int32).reshape(-1).contiguous()
+        td = torch.as_tensor(td_error).detach().to(dev, torch.float32).reshape(-1).contiguous()
+        if td.numel() != leaf.numel():
+            raise ValueError("leaf and td_error must hold one value per sample")
+        prio_update(self.tree, self._leaves, leaf, td, self.alpha, self.eps)
 
 
     def sequence_indices(self, batch_size, L, generator=None):

@@ -30,6 +30,8 @@ ap.add_argument("--capacity", type=int, default=128)
 ap.add_argument("--updates", type=int, default=64)
 ap.add_argument("--batch-size", type=int, default=1024)
 ap.add_argument("--iters", type=int, default=3)
+ap.add_argument("--prioritized", action="store_true",
+                help="draw by priority (the sum tree is kept current by add) and feed |r| back as the TD error")
 ap.add_argument("--out", default="")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -38,7 +40,11 @@ B, N, W = a.envs, a.assets, a.window
 m = MarketSeries(synth.series(a.days, 1, N, device=dev)[:, 0].contiguous(), device=dev)
 env = TradingEnv(num_envs=B, num_assets=N, window=W, device=dev)
 ap_gen = torch.Generator(device=dev).manual_seed(1)     # sample indices drawn on the GPU
-loop = OffPolicy(env, m, capacity=a.capacity, update=lambda *x: None, batch_size=a.batch_size, generator=ap_gen)
+if a.prioritized:
+    loop = OffPolicy(env, m, capacity=a.capacity, update=lambda s, a_, r, s2, w: r.reshape(-1),
+                     batch_size=a.batch_size, generator=ap_gen, prioritized=True)
+else:
+    loop = OffPolicy(env, m, capacity=a.capacity, update=lambda *x: None, batch_size=a.batch_size, generator=ap_gen)
 gen = torch.Generator().manual_seed(2)
 st = torch.cuda.current_stream()
 E = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
@@ -77,7 +83,7 @@ for it in range(a.iters + 1):
 med = {k: sorted(r[k] for r in res)[len(res) // 2] for k in res[0]}
 S = a.updates * a.batch_size
 doc = {"device": torch.cuda.get_device_name(0), "envs": B, "assets": N, "window": W, "collect_steps": a.steps,
-       "capacity": a.capacity, "updates": a.updates, "batch_size": a.batch_size, "median": med,
+       "capacity": a.capacity, "prioritized": a.prioritized, "updates": a.updates, "batch_size": a.batch_size, "median": med,
        "env_steps_per_s_collect": B * a.steps / (med["collect_ms"] / 1e3),
        "env_steps_per_s_env_only": B * a.steps / (med["env_step_ms"] / 1e3),
        "samples_per_s": S / (med["update_sampling_ms"] / 1e3),

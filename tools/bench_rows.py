@@ -62,9 +62,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default="")
-    ap.add_argument("--only", default="", help="comma list of f1,f2,f3,f4 (default: all)")
+    ap.add_argument("--only", default="", help="comma list of f1,f2,f3,f4,prio (default: all)")
     a = ap.parse_args()
-    only = set(a.only.split(",")) if a.only else {"f1", "f2", "f3", "f4"}
+    only = set(a.only.split(",")) if a.only else {"f1", "f2", "f3", "f4", "prio"}
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     lib = _abi.load()
@@ -356,6 +356,82 @@ def main():
                 res.append(row(f"trajectory_metrics_{mode}", us, alg, T=T, B=B, N=30))
             os.environ.pop("PMENV_METRICS_WALK", None)
             os.environ.pop("PMENV_METRICS_FUSED", None)
+
+    if "prio" in only:
+        # the priority tree on config 3's ring (L = 16,384 envs x 256 rows) beside the torch
+        # statement of the same work on a bare f32 priority array, same process, alternating:
+        # the draw is cumsum in f64 over every leaf + searchsorted + the weights; the update
+        # a pow and a scatter with amax (no tree to maintain: its cost is the draw's cumsum);
+        # the fill two slice assignments. S = 256 is config's batch, 8,192 the gather row's size
+        from pmenv.replay import prio_layout, prio_tree
+        Bp, Hp = 16384, 256
+        Lp = Bp * Hp
+        lay = prio_layout(Lp)
+        tree = prio_tree(Lp, dev)
+        ck(lib.pmenv_prio_fill(P(tree), Lp, -1, 0, Lp, st), "prio_fill")
+        ck(lib.pmenv_prio_fill(P(tree), Lp, 17 * Bp, -1, 5 * Bp, st), "prio_fill")       # some closed rows
+        seed_idx = torch.randint(0, Lp, (1 << 20,), device=dev, generator=g, dtype=torch.int32)
+        seed_td = torch.randn(1 << 20, device=dev, generator=g) * 3
+        ck(lib.pmenv_prio_update(P(tree), Lp, P(seed_idx), P(seed_td), 1 << 20, 0.6, 1e-6, st), "prio_update")
+        leaves_t = tree[64:64 + 4 * Lp].view(torch.float32).clone()                        # the torch side's array
+        nlev = len(lay["levels"]) - 1
+
+        def both(name, hip, ref, alg, **kw):
+            hip()
+            ref()
+            th, tr = [], []
+            for _ in range(5):
+                th.append(timeit(hip, a.reps))
+                tr.append(timeit(ref, a.reps))
+            us, base = statistics.median(th), statistics.median(tr)
+            res.append(row(name + "_torch", base, alg, spread=round((max(tr) - min(tr)) / base, 4), **kw))
+            res.append(row(name, us, alg, ratio=round(us / base, 4), spread=round((max(th) - min(th)) / us, 4),
+                           baseline="torch: " + kw.get("torch", ""), **{k: v for k, v in kw.items() if k != "torch"}))
+
+        for Sp in (256, 8192):
+            u = ((torch.arange(Sp, device=dev, dtype=torch.float64) +
+                  torch.rand(Sp, device=dev, dtype=torch.float64, generator=g)) / Sp).contiguous()
+            lo, ho, eo = (torch.empty(Sp, dtype=torch.int32, device=dev) for _ in range(3))
+            wo = torch.empty(Sp, device=dev)
+            td = torch.randn(Sp, device=dev, generator=g)
+            got = {}
+
+            def sample():
+                ck(lib.pmenv_prio_sample(P(tree), Lp, Bp, P(u), Sp, 0.4, P(lo), P(ho), P(eo), P(wo), st), "prio_sample")
+
+            def sample_torch():
+                c = torch.cumsum(leaves_t.double(), 0)
+                i = torch.searchsorted(c, u * c[-1], right=True).clamp_(max=Lp - 1)
+                pv = leaves_t[i]
+                got["i"], got["w"] = i, (pv.double() / pv.min().double()).pow(-0.4).float()
+            both(f"prio_sample_S{Sp}", sample, sample_torch, Sp * (nlev * 512 + 256 + 8 + 16), S=Sp, L=Lp,
+                 torch="cumsum f64 over the leaves + searchsorted + weights")
+            res[-1]["same_leaves"] = round(float((got["i"].to(torch.int32) == lo).float().mean()), 4)
+
+            def update():
+                ck(lib.pmenv_prio_update(P(tree), Lp, P(lo), P(td), Sp, 0.6, 1e-6, st), "prio_update")
+            li = lo.long()
+
+            def update_torch():
+                leaves_t.scatter_reduce_(0, li, (td.abs().double() + 1e-6).pow(0.6).float(), "amax", include_self=False)
+            both(f"prio_update_S{Sp}", update, update_torch, Sp * (8 + nlev * 520 + 256), S=Sp, L=Lp,
+                 torch="pow + scatter_reduce amax on the bare array (no tree)")
+        state = {"h": 0}
+
+        def fill():
+            h = state["h"]
+            state["h"] = (h + 1) % Hp
+            ck(lib.pmenv_prio_fill(P(tree), Lp, h * Bp, ((h + 100) % Hp) * Bp, Bp, st), "prio_fill")
+
+        def fill_torch():
+            h = state["h"]
+            state["h"] = (h + 1) % Hp
+            leaves_t[h * Bp:(h + 1) * Bp] = 0.0
+            o = (h + 100) % Hp
+            leaves_t[o * Bp:(o + 1) * Bp] = 1.0
+        both("prio_fill_B16384", fill, fill_torch, 2 * Bp * 4 * 2 + 2 * (Bp // 64) * 8, n=Bp, L=Lp,
+             torch="two slice assignments on the bare array (no tree)")
+        del tree, leaves_t
 
     doc = {"device": torch.cuda.get_device_name(0), "peak_GBs": PEAK_GBS, "cases": res}
     print(json.dumps(doc, indent=1))
