@@ -38,7 +38,8 @@ extern "C" {
 /* 3: pmenv_step_host / pmenv_reset_host (host buffers, the reference driver's call shape) */
 /* 4: pmenv_replay_gather_nstep (n-step return samples of the replay ring) */
 /*    (pmenv_replay_gather_seq, sequence samples of the same ring, was added under 4: a new
- *    symbol breaks no caller; pmenv's loader names a symbol that a stale library lacks) */
+ *    symbol breaks no caller; pmenv's loader names a symbol that a stale library lacks;
+ *    pmenv_gae_path, the GAE pass's kernel by name, likewise) */
 #define PMENV_ABI_VERSION 4
 
 /* Opaque HIP stream (identical to HIP's own typedef); NULL = default stream. */
@@ -346,11 +347,21 @@ int pmenv_gae(const float* rewards, const float* values, const uint8_t* dones,
  * chunk publishes its affine map and an epoch-tagged flag in `work`, then composes the
  * later chunks' maps (replaces round 3's two launches). `work` must be 8-B aligned; it
  * may be reused by later calls (each call tags its flags with a fresh epoch) but not
- * shared by two calls in flight. work == NULL, too small or misaligned: as pmenv_gae. */
+ * shared by two calls in flight. work == NULL, too small or misaligned: as pmenv_gae.
+ * Enqueued while `stream` is being captured into a hipGraph: as pmenv_gae too, and `work`
+ * is left untouched — the look-back's epoch is chosen by the host at enqueue time, so a
+ * replayed call would find its own epoch already in the flags and could compose the
+ * previous replay's maps; the tile, scan and loop kernels keep no state between calls. */
 size_t pmenv_gae_workspace(int32_t T, int32_t B);
 int pmenv_gae_ex(const float* rewards, const float* values, const uint8_t* dones,
                  float* adv, float* ret, int32_t T, int32_t B, float gamma, float lam,
                  double* work, size_t work_bytes, hipStream_t stream);
+/* The kernel instantiation a [T, B] call takes outside stream capture, as a static string
+ * ("gae_tile_kernel<8,16,1,2>", "gae_tile_kernel<8,8>", "gae_tile_kernel<8,8,8,2>",
+ * "gae_scan_kernel", "gae_kernel", "gae_lookback_kernel<8,8>", "gae_lookback_kernel<8,16>";
+ * "" for T < 1 or B < 1). pmenv_gae: work_bytes = 0. pmenv_gae_ex: the call's work_bytes
+ * and work_aligned = (work != NULL and 8-B aligned). Host only: launches nothing. */
+const char* pmenv_gae_path(int32_t T, int32_t B, size_t work_bytes, int work_aligned);
 
 /* Per-rank advantage moments {count, sum, sum of squares} in f64 into out[3]
  * (the only cross-GPU exchange: a 24-byte all-reduce over xGMI). `work` is

@@ -1210,43 +1210,6 @@ int pmenv_window_init_days(float* obs, const float* series, int32_t T, int32_t N
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
 
-int pmenv_gae(const float* rewards, const float* values, const uint8_t* dones, float* adv, float* ret, int32_t T,
-              int32_t B, float gamma, float lam, hipStream_t stream) {
-    if (!rewards || !values || !adv || !ret || T < 1 || B < 1) return PMENV_ERR_ARG;
-    int rc = PMENV_OK;
-    if (pmenv_tools::gae(rewards, values, dones, adv, ret, T, B, gamma, lam, stream, &rc)) return rc;
-    // measured on MI355X (tools/bench_rows.py, profiles/rows_r01.json): the tiled scan
-    // beats the per-env loop 2.7x at T = 256 x B = 65536 and 14x at 2048 x 8192; the
-    // wave-per-env scan only for a handful of envs with long horizons
-    const bool fits = (size_t)(T + 1) * (size_t)B * 4u < (1ull << 31);   // gae_tile_kernel's buffer offsets
-    const bool scan = B < 64 && T >= 256;
-    const bool tile = fits && !scan;
-    const int U = B >= 16384 ? 8 : 16;           // steps per lane and segment
-    // many envs and at least four 64-day segments: the tile held to 64 VGPRs (8 waves per
-    // SIMD, so a 65,536-env rollout's 1,024 workgroups are resident at once; the same bits):
-    // 56.7 vs 58.5 us at 256 x 65,536, 110.1 vs 114.7 at 512 x 65,536; slower below 65,536
-    // envs or 256 days (profiles/ab_r02/gae_occ8_r02zl.json)
-    // adv / ret are written once and read by the learner later: nt stores where they measured
-    // faster (the same bits): 62.3 -> 45.7 us at 256 x 65,536, 9.0 -> 8.4 at 256 x 4,096,
-    // 80.2 -> 58.9 at 2,048 x 8,192 on the tile; at 256 x 16,384 (the U = 8 tile, a cache-
-    // resident rollout) 14.1 vs 14.5, so that form keeps plain stores
-    // (profiles/rows_r03ad/rows_nt2.json)
-    if (tile && U == 8 && B >= 65536 && T >= 256)
-        gae_tile_kernel<8, 8, 8, 2><<<(B + 63) / 64, 512, 0, stream>>>(rewards, values, dones, adv, ret, T, B, gamma,
-                                                                      lam);
-    else if (tile && U == 16)
-        gae_tile_kernel<8, 16, 1, 2><<<(B + 63) / 64, 512, 0, stream>>>(rewards, values, dones, adv, ret, T, B, gamma,
-                                                                       lam);
-    else if (tile)
-        gae_tile_kernel<8, 8><<<(B + 63) / 64, 512, 0, stream>>>(rewards, values, dones, adv, ret, T, B, gamma,
-                                                                lam);
-    else if (scan)
-        gae_scan_kernel<<<(B + 3) / 4, 256, 0, stream>>>(rewards, values, dones, adv, ret, T, B, gamma, lam);
-    else
-        gae_kernel<<<(B + 255) / 256, 256, 0, stream>>>(rewards, values, dones, adv, ret, T, B, gamma, lam);
-    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
-}
-
 // Horizon split of the tiled GAE scan: used when the B / 64 env blocks leave CUs idle (few
 // envs, long horizons). Round 4: one pass (gae_lookback_kernel, 64- or 128-day chunks, every chunk
 // composing the later chunks' published maps) in place of the round-3 maps + apply passes
@@ -1280,6 +1243,43 @@ uint64_t gae_next_epoch() {
     }
     return g_gae_epoch.fetch_add(1) + 1;
 }
+
+// The one place that decides which GAE kernel a call takes (pmenv_gae: workspace = false;
+// pmenv_gae_ex: whether the caller's scratch is usable); pmenv_gae_path names it.
+enum gae_kind { kGaeLoop, kGaeScan, kGaeTile16, kGaeTile8, kGaeTile8Occ8, kGaeLb8, kGaeLb16 };
+const char* const kGaeNames[] = {"gae_kernel",
+                                 "gae_scan_kernel",
+                                 "gae_tile_kernel<8,16,1,2>",
+                                 "gae_tile_kernel<8,8>",
+                                 "gae_tile_kernel<8,8,8,2>",
+                                 "gae_lookback_kernel<8,8>",
+                                 "gae_lookback_kernel<8,16>"};
+gae_kind gae_plan(int32_t T, int32_t B, bool workspace) {
+    if (workspace && gae_lb_chunks(T, B)) return gae_lb_seg(T, B) == 128 ? kGaeLb16 : kGaeLb8;
+    // measured on MI355X (tools/bench_rows.py, profiles/rows_r01.json): the tiled scan
+    // beats the per-env loop 2.7x at T = 256 x B = 65536 and 14x at 2048 x 8192; the
+    // wave-per-env scan only for a handful of envs with long horizons
+    const bool fits = (size_t)(T + 1) * (size_t)B * 4u < (1ull << 31);   // gae_tile_kernel's buffer offsets
+    const bool scan = B < 64 && T >= 256;
+    const bool tile = fits && !scan;
+    const int U = B >= 16384 ? 8 : 16;           // steps per lane and segment
+    // many envs and at least four 64-day segments: the tile held to 64 VGPRs (8 waves per
+    // SIMD, so a 65,536-env rollout's 1,024 workgroups are resident at once; the same bits):
+    // 56.7 vs 58.5 us at 256 x 65,536, 110.1 vs 114.7 at 512 x 65,536; slower below 65,536
+    // envs or 256 days (profiles/ab_r02/gae_occ8_r02zl.json)
+    // adv / ret are written once and read by the learner later: nt stores where they measured
+    // faster (the same bits): 62.3 -> 45.7 us at 256 x 65,536, 9.0 -> 8.4 at 256 x 4,096,
+    // 80.2 -> 58.9 at 2,048 x 8,192 on the tile; at 256 x 16,384 (the U = 8 tile, a cache-
+    // resident rollout) 14.1 vs 14.5, so that form keeps plain stores
+    // (profiles/rows_r03ad/rows_nt2.json)
+    if (tile && U == 8 && B >= 65536 && T >= 256) return kGaeTile8Occ8;
+    if (tile && U == 16) return kGaeTile16;
+    if (tile) return kGaeTile8;
+    return scan ? kGaeScan : kGaeLoop;
+}
+bool gae_work_usable(int32_t T, int32_t B, const void* work, size_t work_bytes) {
+    return work && work_bytes >= pmenv_gae_workspace(T, B) && !((uintptr_t)work & 7u);
+}
 }  // namespace
 
 size_t pmenv_gae_workspace(int32_t T, int32_t B) {
@@ -1287,17 +1287,53 @@ size_t pmenv_gae_workspace(int32_t T, int32_t B) {
     return n ? ((size_t)2 * n * B + (size_t)n * ((B + 63) / 64)) * sizeof(double) : 0;
 }
 
+const char* pmenv_gae_path(int32_t T, int32_t B, size_t work_bytes, int work_aligned) {
+    if (T < 1 || B < 1) return "";
+    return kGaeNames[gae_plan(T, B, work_aligned && work_bytes >= pmenv_gae_workspace(T, B))];
+}
+
+int pmenv_gae(const float* rewards, const float* values, const uint8_t* dones, float* adv, float* ret, int32_t T,
+              int32_t B, float gamma, float lam, hipStream_t stream) {
+    if (!rewards || !values || !adv || !ret || T < 1 || B < 1) return PMENV_ERR_ARG;
+    int rc = PMENV_OK;
+    if (pmenv_tools::gae(rewards, values, dones, adv, ret, T, B, gamma, lam, stream, &rc)) return rc;
+    switch (gae_plan(T, B, false)) {
+    case kGaeTile8Occ8:
+        gae_tile_kernel<8, 8, 8, 2><<<(B + 63) / 64, 512, 0, stream>>>(rewards, values, dones, adv, ret, T, B, gamma,
+                                                                      lam);
+        break;
+    case kGaeTile16:
+        gae_tile_kernel<8, 16, 1, 2><<<(B + 63) / 64, 512, 0, stream>>>(rewards, values, dones, adv, ret, T, B, gamma,
+                                                                       lam);
+        break;
+    case kGaeTile8:
+        gae_tile_kernel<8, 8><<<(B + 63) / 64, 512, 0, stream>>>(rewards, values, dones, adv, ret, T, B, gamma,
+                                                                lam);
+        break;
+    case kGaeScan:
+        gae_scan_kernel<<<(B + 3) / 4, 256, 0, stream>>>(rewards, values, dones, adv, ret, T, B, gamma, lam);
+        break;
+    default:
+        gae_kernel<<<(B + 255) / 256, 256, 0, stream>>>(rewards, values, dones, adv, ret, T, B, gamma, lam);
+        break;
+    }
+    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
 int pmenv_gae_ex(const float* rewards, const float* values, const uint8_t* dones, float* adv, float* ret, int32_t T,
                  int32_t B, float gamma, float lam, double* work, size_t work_bytes, hipStream_t stream) {
     if (!rewards || !values || !adv || !ret || T < 1 || B < 1) return PMENV_ERR_ARG;
-    const int n = gae_lb_chunks(T, B);
     int rc = PMENV_OK;
     if (pmenv_tools::gae(rewards, values, dones, adv, ret, T, B, gamma, lam, stream, &rc)) return rc;
-    if (!n || !work || work_bytes < pmenv_gae_workspace(T, B) || ((uintptr_t)work & 7u))
+    const gae_kind kind = gae_plan(T, B, gae_work_usable(T, B, work, work_bytes));
+    // the look-back's epoch is a kernel argument chosen here: a captured call would replay it
+    // on the same workspace, whose flags then already carry it, and a consumer could compose
+    // the previous replay's maps. The tile, scan and loop kernels keep no cross-call state.
+    if ((kind != kGaeLb8 && kind != kGaeLb16) || capturing(stream))
         return pmenv_gae(rewards, values, dones, adv, ret, T, B, gamma, lam, stream);
-    const int neb = (B + 63) / 64;
+    const int n = gae_lb_chunks(T, B), neb = (B + 63) / 64;
     uint64_t* flags = reinterpret_cast<uint64_t*>(work + (size_t)2 * n * B);
-    if (gae_lb_seg(T, B) == 128)
+    if (kind == kGaeLb16)
         gae_lookback_kernel<8, 16><<<(unsigned)(n * neb), 512, 0, stream>>>(rewards, values, dones, adv, ret, T, B,
                                                                           gamma, lam, n, work, flags, gae_next_epoch());
     else

@@ -42,6 +42,14 @@ def gae(rewards, values, dones=None, gamma=0.99, lam=0.95):
     return adv, ret
 
 
+def gae_path(T, B, workspace=True):
+    """The kernel instantiation `gae` runs for a [T, B] rollout (workspace=False: the one
+    pmenv_gae runs, and pmenv_gae_ex without usable scratch or under stream capture)."""
+    lib = _abi.load()
+    nbytes = lib.pmenv_gae_workspace(T, B) if workspace else 0
+    return lib.pmenv_gae_path(T, B, nbytes, 1 if workspace else 0).decode()
+
+
 def moments(x):
     """{count, sum, sum of squares} of x in f64 (device tensor [3])."""
     lib = _abi.load()

@@ -784,7 +784,7 @@ def test_gpu_synth_matches_oracle():
 @pytest.mark.parametrize("T,B,kernel", [(300, 10, "scan"), (257, 63, "scan"), (1, 5, "tile16"), (63, 2, "tile16"),
                                         # tiled: T below / across / not a multiple of the segment, ragged B
                                         (37, 100, "tile16"), (64, 64, "tile16"), (129, 4099, "tile16"),
-                                        (300, 130, "tile16"), (256, 65536, "tile8"), (37, 16385, "tile8"),
+                                        (300, 130, "tile16"), (256, 65536, "tile8_occ8"), (37, 16385, "tile8"),
                                         # from 8,192 envs long horizons take the tile, not the split
                                         (2048, 8192, "tile16"),
                                         # the 64-VGPR tile (B >= 65,536, T >= 256): ragged B, T past a segment
@@ -795,6 +795,8 @@ def test_gpu_gae_kernels_match_oracle(T, B, kernel):
     16- or 8-step lane segments) vs the oracle's sequential recursion (parity unpinned
     by the reference)."""
     from pmenv import rollout
+    assert rollout.gae_path(T, B) == {"scan": "gae_scan_kernel", "tile16": "gae_tile_kernel<8,16,1,2>",
+                                      "tile8": "gae_tile_kernel<8,8>", "tile8_occ8": "gae_tile_kernel<8,8,8,2>"}[kernel]
     rng = np.random.default_rng(T + B)
     r = rng.standard_normal((T, B)).astype(np.float32)
     v = rng.standard_normal((T + 1, B)).astype(np.float32)
