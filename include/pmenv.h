@@ -39,7 +39,8 @@ extern "C" {
 /* 4: pmenv_replay_gather_nstep (n-step return samples of the replay ring) */
 /*    (pmenv_replay_gather_seq, sequence samples of the same ring, was added under 4: a new
  *    symbol breaks no caller; pmenv's loader names a symbol that a stale library lacks;
- *    pmenv_gae_path, the GAE pass's kernel by name, likewise) */
+ *    pmenv_gae_path, the GAE pass's kernel by name, likewise; pmenv_restart_days, per-env
+ *    episodes on the resident series, likewise) */
 #define PMENV_ABI_VERSION 4
 
 /* Opaque HIP stream (identical to HIP's own typedef); NULL = default stream. */
@@ -146,6 +147,26 @@ int pmenv_get_cfg(const pmenv* h, pmenv_cfg* out);
  * mask [B] (uint8, device) selects which envs reset; NULL resets all.
  * obs may be NULL (state-only reset). */
 int pmenv_reset(pmenv* h, float* obs, const uint8_t* mask, hipStream_t stream);
+
+/* Per-env episodes on a resident series (pmenv_step_args.day): call after every such step.
+ * day, end, restart, done: device arrays of B elements; series [series_days, N, F-1], the
+ * one the steps read; obs the window the preceding step left (in place, or its obs_out).
+ * On entry day[b] is the bar that step appended. With next = day[b] + 1:
+ *   next <  end[b]: day[b] = next, done[b] = 0; nothing else of env b is read or written.
+ *   next >= end[b]: done[b] = 1 and env b restarts: obs[b, n, t, f] = series[restart[b] + t, n, f]
+ *     for f < F-1 (days outside the series: NaN, as pmenv_window_init_days), channel F-1 and
+ *     the state (value, counter, statistics, ring, w', last closes) as pmenv_window_init_days
+ *     followed by pmenv_reset(obs, mask) leave them, and day[b] = restart[b] + W, the next
+ *     bar to append. The non-finite counter is not touched.
+ * end[b] is one past the last bar env b may append; the caller keeps end[b] <= series_days
+ * and restart[b] + W < end[b] (not checked on the device). One launch whose work is
+ * proportional to the envs that restart; enqueues on `stream`, never synchronises, allocates
+ * or frees, hipGraph-capturable. Like pmenv_reset it leaves the flat and relay steps' copies
+ * stale on every call (they re-prime on the next step). NULL obs, series, day, end, restart
+ * or done: PMENV_ERR_ARG. */
+int pmenv_restart_days(pmenv* h, float* obs, const float* series, int32_t series_days,
+                       int32_t* day, const int32_t* end, const int32_t* restart,
+                       uint8_t* done, hipStream_t stream);
 
 /* Optional per-step outputs (the reference's info dict, trading_env.py:80,85,90,100). */
 typedef struct pmenv_step_args {

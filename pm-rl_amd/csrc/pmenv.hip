@@ -24,6 +24,7 @@
 
 #include "../../include/pmenv.h"
 #include "data.h"
+#include "episode.h"
 #include "handle.h"
 #include "launch.h"
 #include "prio.h"
@@ -713,6 +714,36 @@ int pmenv_reset(pmenv* h, float* obs, const uint8_t* mask, hipStream_t stream) {
     if (const int rc = flat1_invalidate(h, stream)) return rc;
     reset_kernel<<<h->cfg.num_envs, kBlock, 0, stream>>>(p, obs, mask);
     return check_launch(h, "reset_kernel");
+}
+
+int pmenv_restart_days(pmenv* h, float* obs, const float* series, int32_t series_days, int32_t* day,
+                       const int32_t* end, const int32_t* restart, uint8_t* done, hipStream_t stream) {
+    if (!h) return PMENV_ERR_ARG;
+    h->dev_pending = true;                          // device work of this handle may be in flight
+    const void* ptrs[6] = {obs, series, day, end, restart, done};
+    static const char* const names[6] = {"obs", "series", "day", "end", "restart", "done"};
+    for (int i = 0; i < 6; ++i) {
+        if (!ptrs[i]) { set_err(h, "pmenv_restart_days: %s is required", names[i]); return PMENV_ERR_ARG; }
+        if (i < 5 && !aligned4(ptrs[i])) {          // done is bytes
+            set_err(h, "pmenv_restart_days: %s not 4-byte aligned", names[i]);
+            return PMENV_ERR_ALIGN;
+        }
+    }
+    if (series_days < 1) { set_err(h, "pmenv_restart_days: series_days must be >= 1"); return PMENV_ERR_ARG; }
+    DeviceGuard g(h->device);
+    StepParams p = base_params(h);
+    // unconditional: with staggered envs some env restarts on nearly every call
+    if (const int rc = flat1_invalidate(h, stream)) return rc;
+    const pmenv_cfg& c = h->cfg;
+    const unsigned grid = (unsigned)((c.num_envs + kEpSlice - 1) / kEpSlice);
+    const size_t slab = (size_t)c.window * c.num_assets * 16;
+    const bool staged = c.features == 5 && ((int64_t)c.num_assets * c.window * 5) % 4 == 0 &&
+                        (((uintptr_t)obs | (uintptr_t)series | (uintptr_t)h->ring) & 15u) == 0 &&
+                        kEpMaskBytes + slab <= kEpLdsMax;
+    const auto kernel = staged ? restart_days_kernel<true> : restart_days_kernel<false>;
+    kernel<<<grid, kEpBlock, kEpMaskBytes + (staged ? slab : 0), stream>>>(p, obs, series, series_days, day, end,
+                                                                          restart, done);
+    return check_launch(h, "restart_days_kernel");
 }
 
 int pmenv_step_ex(pmenv* h, const pmenv_step_args* a, hipStream_t stream) {

@@ -16,8 +16,8 @@ LIB_PATH = os.environ.get("PMENV_LIB", os.path.join(HERE, "libpmenv.so"))
 PMENV_ABI_VERSION = 4   # 2: pmenv_window_written / pmenv_state_written; cfg default ret_mode GROSS
                         # 3: pmenv_step_host / pmenv_reset_host
                         # 4: pmenv_replay_gather_nstep
-                        #    (pmenv_replay_gather_seq and pmenv_prio_* added under 4: load() names a
-                        #    missing symbol)
+                        #    (pmenv_replay_gather_seq, pmenv_prio_* and pmenv_restart_days added under 4:
+                        #    load() names a missing symbol)
 
 # enums (include/pmenv.h)
 REWARD_KINDS = {"log_returns": 0, "returns": 1, "sharpe_ratio": 2, "diff_sharpe": 3}
@@ -68,6 +68,7 @@ SIGNATURES = [
     ("pmenv_last_error", ctypes.c_char_p, [_P]),
     ("pmenv_get_cfg", ctypes.c_int, [_P, ctypes.POINTER(PmenvCfg)]),
     ("pmenv_reset", ctypes.c_int, [_P, _P, _P, _P]),
+    ("pmenv_restart_days", ctypes.c_int, [_P, _P, _P, _I32, _P, _P, _P, _P, _P]),
     ("pmenv_step_ex", ctypes.c_int, [_P, ctypes.POINTER(PmenvStepArgs), _P]),
     ("pmenv_step", ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     ("pmenv_step_host", ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),

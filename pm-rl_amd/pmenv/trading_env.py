@@ -12,6 +12,8 @@ call, with a leading batch dimension B of lockstep envs:
     .value                            :9,89    .value  (f64 [B], device view; host 0-dim with host I/O)
     .weights (ActionBuffer)           :10      .weights (RingView: get_last / get_all)
     .info values/actions/rewards/returns       .info (kept by default for one env, as the reference)
+    (the driver resets at the series' end,     restart(features, episodes) -> done  (per-env episodes on
+     on_policy.py:59-67)                         a resident series: pmenv.episodes)
 
 `TradingEnv()` with no arguments is the reference's constructor (`train/on_policy.py:35`):
 the reference sizes its ring from config/base.py's NUM_ASSETS / WINDOW_SIZE and takes
@@ -396,6 +398,41 @@ class TradingEnv:
         if mask is None:
             self._reset_info()
         return features
+
+    def restart(self, features, episodes):
+        """Per-env episodes (pmenv.episodes.Episodes): call after every step(series=,
+        day=episodes.next_day) with the window that step left. One pmenv_restart_days launch
+        on the current stream: an env whose episode ended gets its restart day's window and
+        the reset state, every other env only its day counter one higher. Returns
+        episodes.done (uint8 [B], the same tensor every call). `info` is not tracked across
+        restarts: an env that keeps it raises."""
+        if not torch.is_tensor(features) or not features.is_cuda:
+            raise ValueError("restart needs the device window (per-env episodes run on the GPU only)")
+        if self._obs_check(features):
+            raise ValueError("restart needs the batched window [B, N, W, F]")
+        if self.track_info:
+            raise ValueError("restart does not keep `info` across episodes: build the env with track_info=False")
+        cfg = self.cfg
+        sb = episodes.bars
+        if sb is None or sb.dim() != 3 or sb.shape[1] != cfg.num_assets or sb.shape[2] != cfg.features - 1 or \
+                sb.dtype != torch.float32 or not sb.is_contiguous() or sb.device != self.device:
+            raise ValueError(f"episodes must hold a contiguous float32 [T, {cfg.num_assets}, {cfg.features - 1}] "
+                             f"series on {self.device}")
+        for name in ("next_day", "end", "restart", "done"):
+            t = getattr(episodes, name)
+            if t.device != self.device or t.numel() != cfg.num_envs or not t.is_contiguous() or \
+                    t.dtype != (torch.uint8 if name == "done" else torch.int32):
+                raise ValueError(f"episodes.{name} must hold one element per env on {self.device}")
+        self._hval = None
+        _abi.check(self._lib.pmenv_restart_days(self._h, _ptr(features), _ptr(sb), sb.shape[0],
+                                                _ptr(episodes.next_day), _ptr(episodes.end), _ptr(episodes.restart),
+                                                _ptr(episodes.done), self._stream()), self._h, "pmenv_restart_days")
+        # the launch wrote the state and the window: not a caller edit for the next step's check
+        self._state_ver = _version(self._state)
+        self._watch(features)
+        self._host_io = self._unbatched = False
+        episodes._restarted()
+        return episodes.done
 
     def step(self, action, features, prices=None, bar=None, out=None, series=None, day=None, weights_out=None):
         """trading_env.py:44-105 for all B envs in one kernel launch.
