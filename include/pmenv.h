@@ -40,7 +40,8 @@ extern "C" {
 /*    (pmenv_replay_gather_seq, sequence samples of the same ring, was added under 4: a new
  *    symbol breaks no caller; pmenv's loader names a symbol that a stale library lacks;
  *    pmenv_gae_path, the GAE pass's kernel by name, likewise; pmenv_restart_days, per-env
- *    episodes on the resident series, likewise) */
+ *    episodes on the resident series, likewise; pmenv_replay_path, the sample gathers'
+ *    kernel by name, likewise) */
 #define PMENV_ABI_VERSION 4
 
 /* Opaque HIP stream (identical to HIP's own typedef); NULL = default stream. */
@@ -470,6 +471,27 @@ int pmenv_replay_gather_seq(const float* series, int32_t T, int32_t N, int32_t F
                             const int32_t* row_episode /* [H], NULL = one episode */,
                             int32_t oldest, int32_t count, int32_t L, int32_t time_major,
                             float* x, float* a_out, float* r_out, int32_t* length, hipStream_t stream);
+
+/* The kernel and the launch geometry a sample gather takes for a shape, from the plan the
+ * gathers themselves switch on. kind: which gather (PMENV_REPLAY_ROLLOUT: pmenv_rollout_gather,
+ * declared below); n: pmenv_replay_gather_nstep's n or pmenv_replay_gather_seq's L (ignored by
+ * the other two); aligned: bit 0 = the window outputs (s, s_next / x) are 16-B aligned, bit 1
+ * = series is; cus: the device's compute units, <= 0 for the calling process's current device
+ * (with a count given the call touches no device). Returns a thread-local string, valid
+ * until the thread's next call: the kernel's name as the library instantiates it, then
+ * space-separated R= (asset rows per group, 0 for a form without groups), D= (staged days)
+ * and Lc= nc= (elements per chunk, chunks per sequence) where the form has them, grid=XxY
+ * and lds= (dynamic LDS bytes), e.g. "replay_seq_f5p_kernel<8,16> R=30 D=54 Lc=4 nc=16
+ * grid=256x1 lds=32416"; "" for a shape the gather rejects or an unknown kind. Host only:
+ * launches nothing. */
+typedef enum pmenv_replay_kind {
+    PMENV_REPLAY_ONE_STEP = 0,
+    PMENV_REPLAY_NSTEP = 1,
+    PMENV_REPLAY_SEQ = 2,
+    PMENV_REPLAY_ROLLOUT = 3
+} pmenv_replay_kind;
+const char* pmenv_replay_path(int32_t kind, int32_t N, int32_t F, int32_t W, int32_t n, int32_t S,
+                              int32_t aligned, int32_t cus);
 
 /* ---- prioritized sampling over the same ring. agent/td3/td3.py:39 builds
  * PrioritizedReplayBuffer(buffer_size, alpha, beta, beta_incr), :118 reads `samples, idxs,

@@ -187,6 +187,19 @@ inline pmenv_dev::StepParams base_params(const pmenv* h) {
 
 inline bool aligned4(const void* ptr) { return ((uintptr_t)ptr & 3u) == 0; }
 
+// the current device's compute units, for the handle-less entry points that launch one
+// workgroup per CU: queried once per process, 256 where the query fails
+inline int device_cus() {
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+            n = 256;
+        return n;
+    }();
+    return cus;
+}
+
 // the relay step's deferral list ({epoch, count} + one entry per tile) and tile claims, 16-B padded
 inline size_t relay_list_bytes(const pmenv* h) {
     const size_t tiles = h->relay_tiles;

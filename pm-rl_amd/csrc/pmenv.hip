@@ -4,7 +4,8 @@
 // step, one workgroup per env), env_step.h (scalar step, window streams, reset,
 // fallbacks), scalar_vec.h (packed scalar step), data.h (synthetic market data),
 // rollout.h (GAE, moments), replay.h (replay gather, metrics) and trainer.h (batched
-// reward); the step's launchers in launch.h, the handle and its shape planning in handle.h.
+// reward); the step's launchers in launch.h, the handle and its shape planning in handle.h,
+// the sample gathers' kernel choice in replay_plan.h.
 //
 // Every entry point enqueues on the caller's stream and never synchronises, allocates or
 // frees (graph-capturable), except create / destroy / the explicit synchronous queries
@@ -21,6 +22,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <type_traits>
 
 #include "../../include/pmenv.h"
 #include "data.h"
@@ -29,6 +31,7 @@
 #include "launch.h"
 #include "prio.h"
 #include "replay.h"
+#include "replay_plan.h"
 #include "rollout.h"
 #include "trainer.h"
 
@@ -58,6 +61,18 @@ int pick_k1_vec(const pmenv_cfg& c) {
     if (N <= 256) return kK1Str + 6404;
     if (N <= 512) return kK1Str + 6408;
     return 0;
+}
+
+// calls f(std::integral_constant<int, V>()) for the V among Vs that equals v: a planned
+// pairs-per-thread or store-policy value becomes a kernel's template argument
+template <int... Vs, class Fn>
+void with_const(int v, Fn&& f) {
+    (void)((v == Vs && (f(std::integral_constant<int, Vs>()), true)) || ...);
+}
+// replay_plan's `aligned` bits: every window output, and the series, 16-B aligned
+int replay_aligned(const void* out0, const void* out1, const void* series) {
+    return ((((uintptr_t)out0 | (uintptr_t)out1) & 15u) == 0 ? kReplayOutAligned : 0) |
+           (((uintptr_t)series & 15u) == 0 ? kReplaySeriesAligned : 0);
 }
 
 // the stream is being captured into a hipGraph: step_flat_kernel's host-chosen parity
@@ -1384,6 +1399,19 @@ int pmenv_moments(const float* x, int64_t n, double* out, double* work, hipStrea
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
 
+// ---- the sample gathers: replay_plan.h decides the kernel and its geometry, the entry points
+// validate, plan and launch; pmenv_replay_path names the plan
+const char* pmenv_replay_path(int32_t kind, int32_t N, int32_t F, int32_t W, int32_t n, int32_t S, int32_t aligned,
+                              int32_t cus) {
+    thread_local char text[160];
+    text[0] = 0;
+    const bool has_n = kind == PMENV_REPLAY_NSTEP || kind == PMENV_REPLAY_SEQ;
+    if (N < 1 || F < 2 || W < 1 || S < 1 || (has_n && n < 1) || aligned < 0 || aligned > 3) return text;
+    const ReplayPlan plan = replay_plan(kind, N, F, W, n, S, aligned, cus > 0 ? cus : device_cus());
+    replay_plan_describe(kind, plan, text, sizeof(text));
+    return text;
+}
+
 int pmenv_replay_gather(const float* series, int32_t T, int32_t N, int32_t F, int32_t W, const int32_t* days,
                         const float* actions, const float* rewards, int32_t H, int32_t B, const int32_t* h0,
                         const int32_t* env, int32_t S, float* s, float* s_next, float* a_out, float* r_out,
@@ -1395,61 +1423,26 @@ int pmenv_replay_gather(const float* series, int32_t T, int32_t N, int32_t F, in
     if (pmenv_tools::replay_gather(series, T, N, F, W, days, actions, rewards, H, B, h0, env, S, s, s_next, a_out,
                                    r_out, stream, &rc))
         return rc;
-    // F = 5: vector staging per asset group (replay_gather_f5p_kernel, persistent; or
-    // replay_gather_f5_kernel, one workgroup per sample); otherwise one workgroup per
-    // sample with the W+1 staged days in LDS when they fit in 64 KiB, else one thread per
-    // output float. Measured at S = 8,192, N = 30, W = 50: 96-102 us for the persistent
-    // f5 form, 117 us one workgroup per sample, 204 us for the per-element staging
-    // (tools/ab_replay.py, bench_rows.py)
-    const size_t lds = (size_t)N * (W + 1) * F * sizeof(float);
-    const bool al16 = ((uintptr_t)s & 15u) == 0 && ((uintptr_t)s_next & 15u) == 0 && ((uintptr_t)series & 15u) == 0;
-    // F = 5 vector staging over asset groups of R rows: R divides N, R*W*F is a multiple
-    // of 4 (16-B aligned groups), R*(W+1) <= 2,048 (day, asset) pairs (at most 8 per
-    // thread); N = 30, W = 50: R = 30, one group per sample
-    int R = 0;
-    if (F == 5 && al16) {
-        // the largest group within 2,048 pairs: whole samples measured faster than
-        // 10-asset groups (131 vs 148 us at N = 30, W = 50) — every workgroup pays the
-        // sample's dependent index loads once
-        for (int r = N; r >= 1; --r)
-            if (N % r == 0 && ((int64_t)r * W * F) % 4 == 0 && (int64_t)r * (W + 1) <= 2048 && r <= 256) {
-                R = r;
-                break;
-            }
-    }
-    if (R > 0) {
-        const FastDiv dr = make_fastdiv((uint32_t)R), dwf = make_fastdiv((uint32_t)(W * F));
-        const size_t glds = (size_t)R * (W + 1) * F * sizeof(float);
-        const int pairs = R * (W + 1);
-        // s / s' are written once per sample: nt stores, 129.6 -> 118.6 us at S = 8,192
-        // (tools/ab_replay.py, profiles/ab_r01/replay_nt_tpb_r01h.log). Persistent form
-        // (replay_gather_f5p_kernel): one workgroup per CU loops over the samples with the
-        // next sample's loads in flight. One per CU is the measured optimum (S = 8,192:
-        // 96 us at 256 workgroups; 114-121 us at 192, 288, 512, 768, 1,280 and one
-        // workgroup per sample, 117 us; profiles/ab_r01/replay_grid_r01j.log).
-        static int cus = 0;
-        if (!cus) {
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess ||
-                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-                cus = 256;
-        }
-        const int gy = N / R;
-        const int G = cus / gy > 0 ? cus / gy : 1;
-        const dim3 pgrid((unsigned)(S < G ? S : G), (unsigned)(N / R));
-        const int ppt = pairs <= 2 * 256 ? 2 : pairs <= 4 * 256 ? 4 : 8;
-#define PMENV_RGP(PPT)                                                                                        \
-    replay_gather_f5p_kernel<PPT, 2><<<pgrid, 256, glds, stream>>>(series, T, N, W, days, actions, rewards, H, B, \
-                                                                   h0, env, S, s, s_next, a_out, r_out, R, dr, dwf)
-        if (ppt == 2) PMENV_RGP(2); else if (ppt == 4) PMENV_RGP(4); else PMENV_RGP(8);
-#undef PMENV_RGP
-    } else if (lds <= 64 * 1024 && N <= 256 && ((uintptr_t)s & 15u) == 0 && ((uintptr_t)s_next & 15u) == 0) {
-        replay_gather_lds_kernel<<<(unsigned)S, 256, lds, stream>>>(series, T, N, F, W, days, actions, rewards, H, B,
-                                                                   h0, env, s, s_next, a_out, r_out);
-    } else {
-        const int64_t threads = (int64_t)S * N * W * F;
-        replay_gather_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(
-            series, T, N, F, W, days, actions, rewards, H, B, h0, env, S, s, s_next, a_out, r_out);
+    const ReplayPlan plan =
+        replay_plan(PMENV_REPLAY_ONE_STEP, N, F, W, 1, S, replay_aligned(s, s_next, series), device_cus());
+    const dim3 grid(plan.grid_x, plan.grid_y);
+    switch (plan.form) {
+    case kReplayF5p:
+        with_const<2, 4, 8>(plan.ppt, [&](auto ppt) {
+            replay_gather_f5p_kernel<decltype(ppt)::value, 2><<<grid, plan.block, plan.lds_bytes, stream>>>(
+                series, T, N, W, days, actions, rewards, H, B, h0, env, S, s, s_next, a_out, r_out, plan.R,
+                make_fastdiv((uint32_t)plan.R), make_fastdiv((uint32_t)(W * F)));
+        });
+        break;
+    case kReplayLds:
+        replay_gather_lds_kernel<<<grid, plan.block, plan.lds_bytes, stream>>>(
+            series, T, N, F, W, days, actions, rewards, H, B, h0, env, s, s_next, a_out, r_out);
+        break;
+    case kReplayElem:
+        replay_gather_kernel<<<grid, plan.block, 0, stream>>>(series, T, N, F, W, days, actions, rewards, H, B, h0,
+                                                             env, S, s, s_next, a_out, r_out);
+        break;
+    default: return PMENV_ERR_ARG;
     }
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
@@ -1464,57 +1457,27 @@ int pmenv_replay_gather_nstep(const float* series, int32_t T, int32_t N, int32_t
         count > H || oldest < 0 || oldest >= H || !(gamma > 0.0f && gamma <= 1.0f))
         return PMENV_ERR_ARG;
     const NstepRing rg{row_episode, oldest, count, n, (double)gamma};
-    // the staged image holds the union of two overlapping windows: W + min(n, W) days.
-    // Same forms and the same asset-group rule as pmenv_replay_gather with that image:
-    // R divides N, R*W*F is a multiple of 4, at most 12 (day, asset) pairs per thread
-    // (N = 30, W = 50 keeps whole samples up to the disjoint case, 3,000 pairs), the
-    // image within 64 KiB. Measured at config 3's shape (S = 8,192, N = 30, W = 50) beside
-    // the one-step gather's 97 us: 122 us at n = 1, 126 us at n = 5, 245 us at n = 64
-    // (tools/bench_rows.py, profiles/rows_nstep.json). The generic LDS form has the
-    // one-step generic form's structure, which runs 198 us there: slower than the fast
-    // form at n <= 5 already on the one-step figure, and not timed at n = 64.
-    const int D = W + (n < W ? n : W);
-    const size_t lds = (size_t)N * D * F * sizeof(float);
-    const bool al16 = ((uintptr_t)s & 15u) == 0 && ((uintptr_t)s_next & 15u) == 0 && ((uintptr_t)series & 15u) == 0;
-    int R = 0;
-    if (F == 5 && al16) {
-        for (int r = N; r >= 1; --r)
-            if (N % r == 0 && ((int64_t)r * W * F) % 4 == 0 && (int64_t)r * D <= 12 * 256 && r <= 256 &&
-                (size_t)r * D * F * sizeof(float) <= 64 * 1024) {
-                R = r;
-                break;
-            }
-    }
-    if (R > 0) {
-        const FastDiv dr = make_fastdiv((uint32_t)R), dwf = make_fastdiv((uint32_t)(W * F));
-        const size_t glds = (size_t)R * D * F * sizeof(float);
-        const int pairs = R * D;
-        static int cus = 0;                                // one workgroup per CU, as the one-step gather
-        if (!cus) {
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess ||
-                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-                cus = 256;
-        }
-        const int gy = N / R;
-        const int G = cus / gy > 0 ? cus / gy : 1;
-        const dim3 pgrid((unsigned)(S < G ? S : G), (unsigned)gy);
-        const int ppt = pairs <= 2 * 256 ? 2 : pairs <= 4 * 256 ? 4 : pairs <= 8 * 256 ? 8 : 12;
-#define PMENV_RNP(PPT)                                                                                         \
-    replay_nstep_f5p_kernel<PPT, 2><<<pgrid, 256, glds, stream>>>(series, T, N, W, days, actions, rewards, H, B, \
-                                                                  h0, env, S, rg, D, s, s_next, a_out, r_out,  \
-                                                                  steps, discount, R, dr, dwf)
-        if (ppt == 2) PMENV_RNP(2); else if (ppt == 4) PMENV_RNP(4); else if (ppt == 8) PMENV_RNP(8); else PMENV_RNP(12);
-#undef PMENV_RNP
-    } else if (lds <= 64 * 1024 && N <= 256 && ((uintptr_t)s & 15u) == 0 && ((uintptr_t)s_next & 15u) == 0) {
-        replay_nstep_lds_kernel<<<(unsigned)S, 256, lds, stream>>>(series, T, N, F, W, days, actions, rewards, H, B,
-                                                                  h0, env, rg, D, s, s_next, a_out, r_out, steps,
-                                                                  discount);
-    } else {
-        const int64_t threads = (int64_t)S * N * W * F;
-        replay_nstep_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(
-            series, T, N, F, W, days, actions, rewards, H, B, h0, env, S, rg, s, s_next, a_out, r_out, steps,
+    const ReplayPlan plan =
+        replay_plan(PMENV_REPLAY_NSTEP, N, F, W, n, S, replay_aligned(s, s_next, series), device_cus());
+    const dim3 grid(plan.grid_x, plan.grid_y);
+    switch (plan.form) {
+    case kReplayF5p:
+        with_const<2, 4, 8, 12>(plan.ppt, [&](auto ppt) {
+            replay_nstep_f5p_kernel<decltype(ppt)::value, 2><<<grid, plan.block, plan.lds_bytes, stream>>>(
+                series, T, N, W, days, actions, rewards, H, B, h0, env, S, rg, plan.D, s, s_next, a_out, r_out,
+                steps, discount, plan.R, make_fastdiv((uint32_t)plan.R), make_fastdiv((uint32_t)(W * F)));
+        });
+        break;
+    case kReplayLds:
+        replay_nstep_lds_kernel<<<grid, plan.block, plan.lds_bytes, stream>>>(
+            series, T, N, F, W, days, actions, rewards, H, B, h0, env, rg, plan.D, s, s_next, a_out, r_out, steps,
             discount);
+        break;
+    case kReplayElem:
+        replay_nstep_kernel<<<grid, plan.block, 0, stream>>>(series, T, N, F, W, days, actions, rewards, H, B, h0,
+                                                            env, S, rg, s, s_next, a_out, r_out, steps, discount);
+        break;
+    default: return PMENV_ERR_ARG;
     }
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
@@ -1529,83 +1492,29 @@ int pmenv_replay_gather_seq(const float* series, int32_t T, int32_t N, int32_t F
         oldest >= H)
         return PMENV_ERR_ARG;
     const NstepRing rg{row_episode, oldest, count, L, 1.0};
-    static int cus = 0;                                    // one workgroup per CU, as the other gathers
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-    }
     int policy = -1, lc_knob = 0;
     pmenv_tools::replay_seq_knobs(&policy, &lc_knob);
-    // F = 5 fast form (replay_seq_f5p_kernel): asset groups of R rows by the n-step rule — R
-    // divides N, R*W*F is a multiple of 4, at most 12 (day, asset) pairs per thread, the
-    // image [R][W + Lc][5] (+16 B) within 64 KiB — sized so that a chunk holds min(L, 8)
-    // elements, or one where no group does. Lc, the elements per chunk: 8 where the image
-    // holds them, fewer where that leaves a CU without an item (Dreamer's 16 sequences of 64
-    // elements: 4). Measured on config 3's ring: 128 x 64 (nt stores) takes 69 us at Lc = 4
-    // and 8, 72-73 us at 16 and 32, 98 us at 2, 159 us at 1; 16 x 64 (sc1 stores) takes
-    // 10.0 us at 4, 13.4-14.0 us at 2 and 8, 21-37 us at 1, 16 and 32 (tools/bench_rows.py's
-    // PMENV_SEQ_LC rows, profiles/rows_seq_ab.json).
-    const bool al16 = (((uintptr_t)x | (uintptr_t)series) & 15u) == 0;
-    auto group = [&](int lc) {
-        const int64_t D = (int64_t)W + lc;
-        for (int r = N < 256 ? N : 256; r >= 1; --r)
-            if (N % r == 0 && ((int64_t)r * W * F) % 4 == 0 && r * D <= 12 * 256 &&
-                (r * D * F + 4) * sizeof(float) <= 64 * 1024)
-                return r;
-        return 0;
-    };
-    int R = 0;
-    if (F == 5 && al16) {
-        R = group(L < 8 ? L : 8);
-        if (!R) R = group(1);
-    }
-    const int gy = R ? N / R : 1;
-    if (R > 0 && (int64_t)S * gy * L <= (1 << 30)) {
-        int64_t cap = 12 * 256 / R;
-        if (cap > (64 * 1024 / 4 - 4) / (F * R)) cap = (64 * 1024 / 4 - 4) / (F * R);
-        cap -= W;
-        if (cap > 256) cap = 256;
-        if (cap > L) cap = L;
-        int64_t nc = (L + (cap < 8 ? cap : 8) - 1) / (cap < 8 ? cap : 8);
-        const int64_t want = ((int64_t)cus + (int64_t)S * gy - 1) / ((int64_t)S * gy);   // chunks for an item a CU
-        if (nc < want) nc = want < L ? want : L;
-        int Lc = (int)((L + nc - 1) / nc);
-        if (lc_knob > 0) Lc = (int)(lc_knob < cap ? lc_knob : cap);
-        nc = (L + Lc - 1) / Lc;
-        const int items = (int)((int64_t)S * gy * nc);
-        const int D = W + Lc, pairs = R * D;
-        const size_t glds = ((size_t)R * D * F + 4) * sizeof(float);
-        // the windows are written once and read by the learner later: the rollout gather's
-        // rule — sc1 stores while they fit the Infinity Cache, nt stores above — with the
-        // bound where this kernel was measured: 31 MB (16 x 64) 21.7 us sc1, 23.2 nt, 24.4
-        // plain; 245 MB (128 x 64) 50.7 us sc1, 57.2 plain, 69.0 nt (PMENV_SEQ_NT rows,
-        // profiles/rows_seq_ab.json). Above 256 MiB nothing was measured for this kernel:
-        // nt, as the rollout gather's sc1 loses there
-        if (policy < 0) policy = (size_t)S * L * N * W * F * sizeof(float) <= ((size_t)256 << 20) ? 16 : 2;
-        const FastDiv dr = make_fastdiv((uint32_t)R), dwf = make_fastdiv((uint32_t)(W * F));
-        const FastDiv dnc = make_fastdiv((uint32_t)nc), dgy = make_fastdiv((uint32_t)gy);
-        const unsigned grid = (unsigned)(items < cus ? items : cus);
-        const int ppt = pairs <= 2 * 256 ? 2 : pairs <= 4 * 256 ? 4 : pairs <= 8 * 256 ? 8 : 12;
-#define PMENV_RSQ(PPT, NTV)                                                                                       \
-    replay_seq_f5p_kernel<PPT, NTV><<<grid, 256, glds, stream>>>(series, T, N, W, days, actions, rewards, H, B, h0, \
-                                                                 env, S, rg, Lc, (int)nc, time_major, x, a_out,     \
-                                                                 r_out, length, R, dr, dwf, dnc, dgy)
-#define PMENV_RSQ_P(NTV)                                                                                          \
-    do {                                                                                                          \
-        if (ppt == 2) PMENV_RSQ(2, NTV); else if (ppt == 4) PMENV_RSQ(4, NTV);                                    \
-        else if (ppt == 8) PMENV_RSQ(8, NTV); else PMENV_RSQ(12, NTV);                                            \
-    } while (0)
-        if (policy == 16) PMENV_RSQ_P(16); else if (policy == 2) PMENV_RSQ_P(2); else PMENV_RSQ_P(0);
-#undef PMENV_RSQ_P
-#undef PMENV_RSQ
-    } else {
-        const int64_t threads = (int64_t)S * L * N * W * F;
-        const int64_t blocks = (threads + 255) / 256;
-        if (blocks > 0x7FFFFFFF) return PMENV_ERR_ARG;
-        replay_seq_kernel<<<(unsigned)blocks, 256, 0, stream>>>(series, T, N, F, W, days, actions, rewards, H, B, h0,
-                                                               env, S, rg, time_major, x, a_out, r_out, length);
+    const ReplayPlan plan =
+        replay_plan(PMENV_REPLAY_SEQ, N, F, W, L, S, replay_aligned(x, x, series), device_cus(), policy, lc_knob);
+    switch (plan.form) {
+    case kReplayF5p:
+        with_const<2, 4, 8, 12>(plan.ppt, [&](auto ppt) {
+            with_const<16, 2, 0>(plan.policy, [&](auto nt) {
+                replay_seq_f5p_kernel<decltype(ppt)::value, decltype(nt)::value>
+                    <<<plan.grid_x, plan.block, plan.lds_bytes, stream>>>(
+                        series, T, N, W, days, actions, rewards, H, B, h0, env, S, rg, plan.Lc, plan.nc, time_major,
+                        x, a_out, r_out, length, plan.R, make_fastdiv((uint32_t)plan.R),
+                        make_fastdiv((uint32_t)(W * F)), make_fastdiv((uint32_t)plan.nc),
+                        make_fastdiv((uint32_t)plan.gy));
+            });
+        });
+        break;
+    case kReplayElem:
+        replay_seq_kernel<<<plan.grid_x, plan.block, 0, stream>>>(series, T, N, F, W, days, actions, rewards, H, B,
+                                                                 h0, env, S, rg, time_major, x, a_out, r_out,
+                                                                 length);
+        break;
+    default: return PMENV_ERR_ARG;                         // more workgroups than a grid holds
     }
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
@@ -1694,30 +1603,22 @@ int pmenv_rollout_gather(const float* series, int32_t T, int32_t N, int32_t F, i
     if (pmenv_tools::rollout_gather(series, T, N, F, W, start, weights, T_rec, B, ring_mode, t_idx, env, S, s,
                                     stream, &rc))
         return rc;
-    const size_t lds = (size_t)W * N * F * sizeof(float);
-    // market [W][N][4] + weights [W][N]; the tile's 16-B series loads and window stores need
-    // 16-B aligned series / s (C callers may pass sliced views: those take the row form)
-    const bool al16 = (((uintptr_t)series | (uintptr_t)s) & 15u) == 0;
-    const bool tile = F == 5 && (N * W * F) % 4 == 0 && lds <= 64 * 1024 && al16;
-    // the windows are written once and read by the learner later: nt stores (the tile's
-    // bits unchanged), per call 29.0 -> 27.5 us at 4,096 samples, 235.1 -> 196.9 at 32,768,
-    // 74.4 -> 54.3 at 8,192 from a 65,536 x 64 buffer; windows that fit well inside the
-    // Infinity Cache (<= 128 MiB) take sc1 stores instead: 24.1-24.5 us at 4,096 samples
-    // (123 MB), which lose 1.5-2x from 245 MB up (profiles/rows_r03ad/, rows_r03ae/)
-    if (tile) {                                            // one workgroup per sample, staged in LDS
-        const bool small = (size_t)S * N * W * F * sizeof(float) <= ((size_t)128 << 20);
-        auto go = [&](auto kern) {
-            kern<<<(unsigned)S, 256, lds, stream>>>(series, T, N, W, start, weights, B, ring_mode, t_idx, env, s,
-                                                   make_fastdiv((uint32_t)N), make_fastdiv((uint32_t)(W * F)),
-                                                   make_fastdiv((uint32_t)F));
-        };
-        if (small) go(rollout_gather_tile_kernel<16>);
-        else go(rollout_gather_tile_kernel<2>);
-        return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+    const ReplayPlan plan =
+        replay_plan(PMENV_REPLAY_ROLLOUT, N, F, W, 1, S, replay_aligned(s, s, series), device_cus());
+    switch (plan.form) {
+    case kRolloutTile:
+        with_const<16, 2>(plan.policy, [&](auto nt) {
+            rollout_gather_tile_kernel<decltype(nt)::value><<<plan.grid_x, plan.block, plan.lds_bytes, stream>>>(
+                series, T, N, W, start, weights, B, ring_mode, t_idx, env, s, make_fastdiv((uint32_t)N),
+                make_fastdiv((uint32_t)(W * F)), make_fastdiv((uint32_t)F));
+        });
+        break;
+    case kRolloutRows:
+        rollout_gather_rows_kernel<<<plan.grid_x, plan.block, 0, stream>>>(
+            series, T, N, F, W, start, weights, B, ring_mode, t_idx, env, S, s, make_fastdiv((uint32_t)F));
+        break;
+    default: return PMENV_ERR_ARG;
     }
-    const int64_t rows = (int64_t)S * N;                 // one wave per (sample, asset) row
-    rollout_gather_rows_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, stream>>>(
-        series, T, N, F, W, start, weights, B, ring_mode, t_idx, env, S, s, make_fastdiv((uint32_t)F));
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
 

@@ -16,8 +16,8 @@ LIB_PATH = os.environ.get("PMENV_LIB", os.path.join(HERE, "libpmenv.so"))
 PMENV_ABI_VERSION = 4   # 2: pmenv_window_written / pmenv_state_written; cfg default ret_mode GROSS
                         # 3: pmenv_step_host / pmenv_reset_host
                         # 4: pmenv_replay_gather_nstep
-                        #    (pmenv_replay_gather_seq, pmenv_prio_* and pmenv_restart_days added under 4:
-                        #    load() names a missing symbol)
+                        #    (pmenv_replay_gather_seq, pmenv_prio_*, pmenv_restart_days and
+                        #    pmenv_replay_path added under 4: load() names a missing symbol)
 
 # enums (include/pmenv.h)
 REWARD_KINDS = {"log_returns": 0, "returns": 1, "sharpe_ratio": 2, "diff_sharpe": 3}
@@ -52,6 +52,7 @@ class PmenvStepArgs(ctypes.Structure):
 PHASE_SCALAR = 1
 PHASE_ADVANCE = 2
 STEP_PATHS = {"auto": 0, "one_launch": 1, "two_launch": 2, "flat": 3, "relay": 4}
+REPLAY_KINDS = {"one_step": 0, "nstep": 1, "seq": 2, "rollout": 3}   # pmenv_replay_kind
 
 
 # (name, restype, argtypes) for every symbol include/pmenv.h declares
@@ -102,6 +103,7 @@ SIGNATURES = [
     ("pmenv_replay_gather_seq", ctypes.c_int,
      [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, _I32,
       _P, _P, _P, _P, _P]),
+    ("pmenv_replay_path", ctypes.c_char_p, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
     ("pmenv_prio_tree_bytes", _SZ, [_I64]),
     ("pmenv_prio_init", ctypes.c_int, [_P, _I64, _P]),
     ("pmenv_prio_fill", ctypes.c_int, [_P, _I64, _I64, _I64, _I64, _P]),

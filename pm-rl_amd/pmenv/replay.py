@@ -112,6 +112,16 @@ def prio_layout(leaves):
             return dict(header=0, levels=levels, bytes=off)
 
 
+def gather_path(kind, N, W, F=5, n=1, S=1, aligned=3, cus=0):
+    """pmenv_replay_path: the kernel instantiation and launch geometry a sample gather takes,
+    e.g. "replay_gather_f5p_kernel<8,2> R=30 D=51 grid=256x1 lds=30600". kind: "one_step"
+    (`gather`), "nstep" (`gather_nstep`, n = n_step), "seq" (`gather_sequences`, n = L) or
+    "rollout" (pmenv_rollout_gather); aligned: bit 0 = 16-B aligned outputs, bit 1 = 16-B
+    aligned series (torch allocations are both); cus: the compute units to plan for, 0 = the
+    current device's. "" for a shape the gather rejects."""
+    return _abi.load().pmenv_replay_path(_abi.REPLAY_KINDS[kind], N, F, W, n, S, aligned, cus).decode()
+
+
 def _stream(dev):
     return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 

@@ -73,6 +73,9 @@ def test_gpu_off_policy_collect_update_evaluate(B, N, W, steps, cap):
     # sampled batches equal the numpy restatement of replay/buffer.py:39-79
     out = loop.update(3)
     assert len(out) == 3 and len(seen) == 3
+    from pmenv.replay import gather_path
+    form = {(30, 20): "replay_gather_f5p_kernel<4,2> R=30 D=21 ", (7, 6): "replay_gather_lds_kernel R=0 D=7 "}[N, W]
+    assert gather_path("one_step", N, W, S=50).startswith(form)
     h0, e = rb.indices(50, generator=torch.Generator().manual_seed(4))
     s, a, r, s2 = rb.gather(h0, e)
     es, ea, er, es2 = replay_gather(bars, rb.days.cpu().numpy(), rb.actions.cpu().numpy(), rb.rewards.cpu().numpy(),

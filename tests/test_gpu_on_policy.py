@@ -89,6 +89,10 @@ def test_gpu_compact_rollout_rematerialises_the_env_windows(ring, B, N, W, T):
         assert torch.equal(buf.obs(t), obs), f"window after {t} steps"
         assert torch.equal(buf.price_relatives(t), m.bars[start.long() + W + t - 1, :, 3] /
                            m.bars[start.long() + W + t - 2, :, 3])
+    from pmenv.replay import gather_path
+    form = "rollout_gather_tile_kernel<16> R=0 grid=3x1 lds=30000" if (N, W) == (30, 50) else \
+        f"rollout_gather_rows_kernel R=0 grid={(3 * N + 3) // 4}x1 lds=0"
+    assert gather_path("rollout", N, W, S=3) == form
     s, a_, r_, v_prev, a_prev, p = buf.gather(torch.tensor([T, 1, T // 2], device=DEV), torch.tensor([0, B - 1, B // 2],
                                                                                                     device=DEV))
     assert s.shape == (3, N, W, 5) and p.shape == (3, N, 1) and v_prev.shape == (3, 1, 1)
@@ -102,6 +106,7 @@ def test_gpu_compact_rollout_rematerialises_the_env_windows(ring, B, N, W, T):
     raw = torch.full((3 * N * W * 5 + 4,), -1.0, device=DEV)
     mis = raw[1:1 + 3 * N * W * 5]
     assert mis.data_ptr() % 16 == 4
+    assert gather_path("rollout", N, W, S=3, aligned=2).startswith("rollout_gather_rows_kernel ")
     st = ctypes.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
     pp = lambda x: ctypes.c_void_p(x.data_ptr())  # noqa: E731
     _abi.check(_abi.load().pmenv_rollout_gather(pp(m.bars), m.bars.shape[0], N, 5, W, pp(buf.start), pp(buf.w), T, B,

@@ -1016,17 +1016,21 @@ def test_gpu_resident_series_any_F_equals_bar_batch(N, W, F, B, impl, path):
 
 
 @pytest.mark.parametrize("T,N,W,B,H,S", [
-    (200, 30, 12, 33, 40, 64),     # F = 5 vector staging (4 pairs per thread), persistent gather
+    (200, 30, 12, 33, 40, 64),     # F = 5 vector staging (2 pairs per thread), persistent gather
     (300, 30, 50, 17, 80, 64),     # F = 5, 8 pairs per thread (BASELINE shape)
     (200, 30, 12, 33, 40, 1301),   # persistent loop: several samples per workgroup, ragged tail
     (60, 3, 5, 4, 9, 64),          # LDS-staged, sample block not 16-B granular
-    (120, 300, 50, 3, 60, 16)])    # staged days > 64 KiB: per-float kernel
+    (120, 300, 50, 3, 60, 16)])    # N > 256: ten groups of 30 assets per sample (the per-float kernel:
+                                   # test_gpu_replay_nstep.py's 257-asset shape at n = 1)
 def test_gpu_replay_gather_matches_restatement(T, N, W, B, H, S):
     """replay/buffer.py:39-79 sample on device vs the numpy restatement
     (the reference module is not importable: parity restated from its text)."""
     from pmenv import MarketSeries
-    from pmenv.replay import DeviceReplay
+    from pmenv.replay import DeviceReplay, gather_path
     from oracle import replay_gather
+    form = {(30, 12): "replay_gather_f5p_kernel<2,2> R=30 D=13 ", (30, 50): "replay_gather_f5p_kernel<8,2> R=30 D=51 ",
+            (3, 5): "replay_gather_lds_kernel R=0 D=6 ", (300, 50): "replay_gather_f5p_kernel<8,2> R=30 D=51 "}[N, W]
+    assert gather_path("one_step", N, W, S=S).startswith(form)
     rng = np.random.default_rng(4)
     bars = (100 * np.exp(0.01 * rng.standard_normal((T, N, 4)).cumsum(0))).astype(np.float32)
     m = MarketSeries(bars, device=DEV)
@@ -1048,9 +1052,11 @@ def test_gpu_replay_gather_full_size_persistent():
     of 30 assets x 50 days): the persistent gather (one workgroup per CU, ~32 samples
     each, the next sample's loads in flight) vs the restatement on 512 of the samples."""
     from pmenv import MarketSeries
-    from pmenv.replay import DeviceReplay
+    from pmenv.replay import DeviceReplay, gather_path
     from oracle import replay_gather
     B, N, W, H, S, T = 4096, 30, 50, 256, 8192, 700
+    cus = torch.cuda.get_device_properties(DEV).multi_processor_count
+    assert gather_path("one_step", N, W, S=S) == f"replay_gather_f5p_kernel<8,2> R=30 D=51 grid={cus}x1 lds=30600"
     rng = np.random.default_rng(11)
     bars = (100 * np.exp(0.01 * rng.standard_normal((T, N, 4)).cumsum(0))).astype(np.float32)
     m = MarketSeries(bars, device=DEV)

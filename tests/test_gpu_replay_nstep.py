@@ -28,6 +28,21 @@ SHAPES = [(4, 4, 5, 700),      # F = 5 persistent form, several samples per work
           (8, 10, 8, 64),      # generic LDS form
           (300, 4, 5, 64),     # N > 256
           (257, 3, 5, 64)]     # N > 256 and no 16-B granular asset group: one thread per float
+# the kernel each shape takes (pmenv_replay_path, asserted before any value is compared): the
+# start of its name and the asset rows per group; the one-step gather's differ by name only
+FORMS = {(4, 4, 5): ("replay_nstep_f5p_kernel<2,2>", 4),
+         (30, 50, 5): ("replay_nstep_f5p_kernel<", 30),
+         (3, 3, 3): ("replay_nstep_lds_kernel", 0),
+         (8, 10, 8): ("replay_nstep_lds_kernel", 0),
+         (300, 4, 5): ("replay_nstep_f5p_kernel<", 150),
+         (257, 3, 5): ("replay_nstep_kernel", 0)}
+
+
+def assert_form(kind, N, W, F, n, S, form):
+    from pmenv.replay import gather_path
+    name, R = form
+    path = gather_path(kind, N, W, F, n=n, S=S).split(" ")
+    assert path[0].startswith(name) and path[1] == f"R={R}", path
 
 
 @functools.lru_cache(maxsize=None)
@@ -107,6 +122,7 @@ def test_gpu_replay_nstep_matches_composed_restatement(shape, k):
             acc = x + g64 * acc
         eR[j] = acc
         ed[j] = np.prod(np.full(m[j], g64))
+    assert_form("nstep", N, W, F, n, S, FORMS[N, W, F])
     s, a, R, s2, steps, disc = rb.gather_nstep(c["h0_dev"], c["env_dev"], n, GAMMA)
     assert s.shape == (S, N, W, F) and s2.shape == s.shape and a.shape == (S, N, 1) and R.shape == (S, 1, 1)
     assert steps.shape == (S,) and steps.dtype == torch.int32 and disc.shape == (S,)
@@ -118,6 +134,8 @@ def test_gpu_replay_nstep_matches_composed_restatement(shape, k):
     assert (np.abs(R - eR) <= 1e-6 * np.abs(eR) + 1e-9).all()
     assert (np.abs(disc - ed) <= 1e-6 * np.abs(ed) + 1e-9).all()
     if n == 1:                                                               # the one-step gather, bit for bit
+        name, rows = FORMS[N, W, F]
+        assert_form("one_step", N, W, F, 1, S, (name.replace("nstep", "gather"), rows))
         s1, a1, r1, s21 = rb.gather(c["h0_dev"], c["env_dev"])
         out = rb.gather_nstep(c["h0_dev"], c["env_dev"], 1, GAMMA)
         for x, y in zip(out[:4], (s1, a1, r1, s21)):

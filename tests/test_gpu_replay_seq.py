@@ -26,6 +26,13 @@ SHAPES = [(4, 4, 5, 200),      # fast form, many items per workgroup
           (3, 3, 3, 16),       # generic form
           (8, 10, 8, 16),      # generic form
           (300, 4, 5, 16)]     # N > 256
+# the kernel each shape takes (pmenv_replay_path, asserted before any value is compared): the
+# start of its name and the asset rows per group
+FORMS = {(4, 4, 5): ("replay_seq_f5p_kernel<2,16>", 4),
+         (30, 50, 5): ("replay_seq_f5p_kernel<", 30),
+         (3, 3, 3): ("replay_seq_kernel", 0),
+         (8, 10, 8): ("replay_seq_kernel", 0),
+         (300, 4, 5): ("replay_seq_f5p_kernel<", 150)}
 
 
 def l_values(W):
@@ -109,6 +116,9 @@ def test_gpu_replay_seq_matches_one_step_restatement(shape, k, time_major):
     assert (live & (dl - (W - 1) < 0)).any() and (live & (dl >= c["T"])).any()   # windows off both ends of the series
     ex, ea, er = c["ex"][:, :L].copy(), c["ea"][:, :L].copy(), c["er"][:, :L].copy()
     ex[~live], ea[~live], er[~live] = 0.0, 0.0, 0.0                          # the table holds elements up to run >= m
+    from pmenv.replay import gather_path
+    path = gather_path("seq", N, W, F, n=L, S=S).split(" ")
+    assert path[0].startswith(FORMS[N, W, F][0]) and path[1] == f"R={FORMS[N, W, F][1]}", path
     x, a, r, length = rb.gather_sequences(c["h0_dev"], c["env_dev"], L, time_major=time_major)
     lead = (L, S) if time_major else (S, L)
     assert x.shape == lead + (N, W, F) and a.shape == lead + (N,) and r.shape == lead

@@ -16,6 +16,7 @@
 #include "../../pm-rl_amd/csrc/handle.h"
 #include "../../pm-rl_amd/csrc/launch.h"
 #include "../../pm-rl_amd/csrc/replay.h"
+#include "../../pm-rl_amd/csrc/replay_plan.h"
 #include "../../pm-rl_amd/csrc/rollout.h"
 #include "../../pm-rl_amd/csrc/trainer.h"
 #include "ab_kernels.h"
@@ -917,14 +918,8 @@ bool replay_gather(const float* series, int32_t T, int32_t N, int32_t F, int32_t
         return false;
     const size_t lds = (size_t)N * (W + 1) * F * sizeof(float);
     const bool al16 = ((uintptr_t)s & 15u) == 0 && ((uintptr_t)s_next & 15u) == 0 && ((uintptr_t)series & 15u) == 0;
-    int R = 0;
-    if (F == 5 && al16 && !knob("PMENV_REPLAY_LDS")) {
-        for (int r = N; r >= 1; --r)
-            if (N % r == 0 && ((int64_t)r * W * F) % 4 == 0 && (int64_t)r * (W + 1) <= 2048 && r <= 256) {
-                R = r;
-                break;
-            }
-    }
+    // the product's one-step group (replay_plan_one_step)
+    const int R = F == 5 && al16 && !knob("PMENV_REPLAY_LDS") ? replay_group(N, W, F, W + 1, 2048, 64 * 1024, 0) : 0;
     if (R > 0) {
         const FastDiv dr = make_fastdiv((uint32_t)R), dwf = make_fastdiv((uint32_t)(W * F));
         const size_t glds = (size_t)R * (W + 1) * F * sizeof(float);
@@ -934,11 +929,7 @@ bool replay_gather(const float* series, int32_t T, int32_t N, int32_t F, int32_t
         const bool t512 = knob_int("PMENV_REPLAY_TPB", 256) == 512;
         const bool persist = !t512 && knob_int("PMENV_REPLAY_PERSIST", 1) != 0;
         if (persist) {
-            int cus = 0, dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess ||
-                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-                cus = 256;
-            const int gy = N / R;
+            const int cus = device_cus(), gy = N / R;
             int G = cus / gy > 0 ? cus / gy : 1;
             G = knob_int("PMENV_REPLAY_GRID", G) > 0 ? knob_int("PMENV_REPLAY_GRID", G) : G;
             const dim3 pgrid((unsigned)(S < G ? S : G), (unsigned)(N / R));
