@@ -41,7 +41,9 @@ extern "C" {
  *    symbol breaks no caller; pmenv's loader names a symbol that a stale library lacks;
  *    pmenv_gae_path, the GAE pass's kernel by name, likewise; pmenv_restart_days, per-env
  *    episodes on the resident series, likewise; pmenv_replay_path, the sample gathers'
- *    kernel by name, likewise) */
+ *    kernel by name, likewise; pmenv_replay_valid_build, pmenv_replay_valid_select,
+ *    pmenv_replay_gather_nstep_env, pmenv_replay_gather_seq_env and pmenv_prio_fill_env, the
+ *    replay of envs that end their episodes on their own, likewise) */
 #define PMENV_ABI_VERSION 4
 
 /* Opaque HIP stream (identical to HIP's own typedef); NULL = default stream. */
@@ -472,6 +474,56 @@ int pmenv_replay_gather_seq(const float* series, int32_t T, int32_t N, int32_t F
                             int32_t oldest, int32_t count, int32_t L, int32_t time_major,
                             float* x, float* a_out, float* r_out, int32_t* length, hipStream_t stream);
 
+/* ---- per-env episodes: a replay fed by envs that restart on their own (pmenv_restart_days)
+ * keeps env_episode [H, B] int32, the episode id of ring row h for env b, not decreasing
+ * from the oldest row to the newest in every column b. replay/buffer.py:47-59 draws a start
+ * inside one epoch of its [epoch, step] layout and reads the window's rows from that epoch
+ * alone; here "rows st .. st + need - 1 of env b share one episode" is decided per column,
+ * by the first and the last of those rows. need = W + 1 for a one-step or n-step start
+ * (agent/td3/td3.py:94-97 stops its fold at `done`), W + L for a full-length sequence
+ * (agent/dreamer/dreamer.py:77-80); span = max(count - need, 0) start offsets exist. ---- */
+
+/* The map of valid (start, env) pairs (replay/buffer.py:47-59: the starts a draw may
+ * take). bits [span][ceil(B / 64)] u64: bit b & 63 of word (st, b >> 6) is set iff
+ * env_episode[(oldest + st) % H, b] == env_episode[(oldest + st + need - 1) % H, b]; the bits at and beyond B of a row's last word are 0. rowsum [span + 1]
+ * int64: rowsum[0] = 0, rowsum[st + 1] - rowsum[st] = the set bits of row st, rowsum[span] =
+ * the total. Integer arithmetic only: the same bits whatever the dispatch order. span == 0
+ * writes rowsum[0] alone (bits may then be NULL). Both buffers 8-byte aligned
+ * (PMENV_ERR_ALIGN). Enqueues two launches on `stream`; never synchronises or allocates.
+ * PMENV_ERR_ARG: need < 1, count outside [0, H], oldest outside [0, H), a NULL pointer. */
+int pmenv_replay_valid_build(const int32_t* env_episode, int32_t H, int32_t B, int32_t oldest, int32_t count,
+                             int32_t need, uint64_t* bits, int64_t* rowsum, hipStream_t stream);
+/* S exact draws from that map (replay/buffer.py:47-59 draws the epoch, the start and the
+ * env uniformly; here the pair is uniform over the valid set): with total = rowsum[span],
+ * sample j takes k = clamp(floor(u[j] * total), 0, total - 1), u [S] f64, a NaN u counting
+ * as 0, and writes the k-th valid pair in (st ascending, env ascending) order as h0[j] =
+ * (oldest + st) % H and env[j]. total == 0 writes -1 to both for every sample and reads no
+ * bits. One launch, one wave per sample. */
+int pmenv_replay_valid_select(const uint64_t* bits, const int64_t* rowsum, int32_t H, int32_t B, int32_t oldest,
+                              int32_t span, const double* u, int32_t S, int32_t* h0, int32_t* env,
+                              hipStream_t stream);
+/* pmenv_replay_gather_nstep with env_episode [H, B] in place of row_episode [H]
+ * (agent/td3/td3.py:94-97: the fold of sample (h0[j], env[j]) stops where env[j]'s episode
+ * ends): m is decided by column env[j]. The same argument errors and the same plan
+ * (pmenv_replay_path); the plan's F = 5 persistent kernel runs in its build for the [H, B]
+ * id layout (replay_nstep_f5p_env_kernel, replay_seq_f5p_env_kernel: the same template
+ * arguments and geometry), the other forms take the layout as strides. NULL = one episode. */
+int pmenv_replay_gather_nstep_env(const float* series, int32_t T, int32_t N, int32_t F, int32_t W,
+                                  const int32_t* days, const float* actions, const float* rewards,
+                                  int32_t H, int32_t B, const int32_t* h0, const int32_t* env, int32_t S,
+                                  const int32_t* env_episode /* [H, B], NULL = one episode */,
+                                  int32_t oldest, int32_t count, int32_t n, float gamma,
+                                  float* s, float* s_next, float* a_out, float* r_out,
+                                  int32_t* steps, float* discount, hipStream_t stream);
+/* pmenv_replay_gather_seq likewise (agent/dreamer/dreamer.py:77-80: a sequence lies in one
+ * episode of its env): length[j] is decided by column env[j]. */
+int pmenv_replay_gather_seq_env(const float* series, int32_t T, int32_t N, int32_t F, int32_t W,
+                                const int32_t* days, const float* actions, const float* rewards,
+                                int32_t H, int32_t B, const int32_t* h0, const int32_t* env, int32_t S,
+                                const int32_t* env_episode /* [H, B], NULL = one episode */,
+                                int32_t oldest, int32_t count, int32_t L, int32_t time_major,
+                                float* x, float* a_out, float* r_out, int32_t* length, hipStream_t stream);
+
 /* The kernel and the launch geometry a sample gather takes for a shape, from the plan the
  * gathers themselves switch on. kind: which gather (PMENV_REPLAY_ROLLOUT: pmenv_rollout_gather,
  * declared below); n: pmenv_replay_gather_nstep's n or pmenv_replay_gather_seq's L (ignored by
@@ -530,6 +582,13 @@ int pmenv_prio_init(void* tree, int64_t leaves, hipStream_t stream);
  * window became complete opens. */
 int pmenv_prio_fill(void* tree, int64_t leaves, int64_t close_first, int64_t open_first, int64_t n,
                     hipStream_t stream);
+/* pmenv_prio_fill for per-env episodes (replay/buffer.py:47-59: a start is valid inside one
+ * episode of its env): leaf open_first + i opens only where ep_first[i] == ep_last[i], i in
+ * [0, n) — the two rows of env_episode at the start's first and last ring row; the other
+ * leaves of the open range keep their value (0: their row's close). The close range is
+ * pmenv_prio_fill's. PMENV_ERR_ARG also for a NULL ep_first / ep_last with an open range. */
+int pmenv_prio_fill_env(void* tree, int64_t leaves, int64_t close_first, int64_t open_first, int64_t n,
+                        const int32_t* ep_first, const int32_t* ep_last, hipStream_t stream);
 /* S samples (td3.py:118). Sample j takes the target u[j] * total, u[j] in [0, 1) (f64),
  * total = the sum of the top level in the order the descent scans it (a 64-lane prefix
  * scan). At each node the first child with a positive value whose inclusive prefix exceeds

@@ -31,6 +31,7 @@
 #include "launch.h"
 #include "prio.h"
 #include "replay.h"
+#include "replay_valid.h"
 #include "replay_plan.h"
 #include "rollout.h"
 #include "trainer.h"
@@ -1447,23 +1448,27 @@ int pmenv_replay_gather(const float* series, int32_t T, int32_t N, int32_t F, in
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
 
-int pmenv_replay_gather_nstep(const float* series, int32_t T, int32_t N, int32_t F, int32_t W, const int32_t* days,
-                              const float* actions, const float* rewards, int32_t H, int32_t B, const int32_t* h0,
-                              const int32_t* env, int32_t S, const int32_t* row_episode, int32_t oldest,
-                              int32_t count, int32_t n, float gamma, float* s, float* s_next, float* a_out,
-                              float* r_out, int32_t* steps, float* discount, hipStream_t stream) {
+// ids: row_episode [H] (per_env = false) or env_episode [H, B]; NULL = one episode either way
+static int replay_gather_nstep(const float* series, int32_t T, int32_t N, int32_t F, int32_t W, const int32_t* days,
+                               const float* actions, const float* rewards, int32_t H, int32_t B, const int32_t* h0,
+                               const int32_t* env, int32_t S, const int32_t* ids, bool per_env, int32_t oldest,
+                               int32_t count, int32_t n, float gamma, float* s, float* s_next, float* a_out,
+                               float* r_out, int32_t* steps, float* discount, hipStream_t stream) {
     if (!series || !days || !actions || !rewards || !h0 || !env || !s || !s_next || !a_out || !r_out || !steps ||
         !discount || T < 1 || N < 1 || F < 2 || W < 1 || H < W + 1 || B < 1 || S < 1 || n < 1 || count < 0 ||
         count > H || oldest < 0 || oldest >= H || !(gamma > 0.0f && gamma <= 1.0f))
         return PMENV_ERR_ARG;
-    const NstepRing rg{row_episode, oldest, count, n, (double)gamma};
+    const NstepRing rg{ids, oldest, count, n, (double)gamma, ids && per_env ? B : 1, ids && per_env ? 1 : 0};
     const ReplayPlan plan =
         replay_plan(PMENV_REPLAY_NSTEP, N, F, W, n, S, replay_aligned(s, s_next, series), device_cus());
     const dim3 grid(plan.grid_x, plan.grid_y);
     switch (plan.form) {
     case kReplayF5p:
+        // the plan's kernel, built once per id layout (replay.h ring_ep)
         with_const<2, 4, 8, 12>(plan.ppt, [&](auto ppt) {
-            replay_nstep_f5p_kernel<decltype(ppt)::value, 2><<<grid, plan.block, plan.lds_bytes, stream>>>(
+            constexpr int kPpt = decltype(ppt)::value;
+            auto* kernel = ids && per_env ? replay_nstep_f5p_env_kernel<kPpt, 2> : replay_nstep_f5p_kernel<kPpt, 2>;
+            kernel<<<grid, plan.block, plan.lds_bytes, stream>>>(
                 series, T, N, W, days, actions, rewards, H, B, h0, env, S, rg, plan.D, s, s_next, a_out, r_out,
                 steps, discount, plan.R, make_fastdiv((uint32_t)plan.R), make_fastdiv((uint32_t)(W * F)));
         });
@@ -1482,16 +1487,35 @@ int pmenv_replay_gather_nstep(const float* series, int32_t T, int32_t N, int32_t
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
 
-int pmenv_replay_gather_seq(const float* series, int32_t T, int32_t N, int32_t F, int32_t W, const int32_t* days,
-                            const float* actions, const float* rewards, int32_t H, int32_t B, const int32_t* h0,
-                            const int32_t* env, int32_t S, const int32_t* row_episode, int32_t oldest, int32_t count,
-                            int32_t L, int32_t time_major, float* x, float* a_out, float* r_out, int32_t* length,
-                            hipStream_t stream) {
+int pmenv_replay_gather_nstep(const float* series, int32_t T, int32_t N, int32_t F, int32_t W, const int32_t* days,
+                              const float* actions, const float* rewards, int32_t H, int32_t B, const int32_t* h0,
+                              const int32_t* env, int32_t S, const int32_t* row_episode, int32_t oldest,
+                              int32_t count, int32_t n, float gamma, float* s, float* s_next, float* a_out,
+                              float* r_out, int32_t* steps, float* discount, hipStream_t stream) {
+    return replay_gather_nstep(series, T, N, F, W, days, actions, rewards, H, B, h0, env, S, row_episode, false,
+                               oldest, count, n, gamma, s, s_next, a_out, r_out, steps, discount, stream);
+}
+
+int pmenv_replay_gather_nstep_env(const float* series, int32_t T, int32_t N, int32_t F, int32_t W,
+                                  const int32_t* days, const float* actions, const float* rewards, int32_t H,
+                                  int32_t B, const int32_t* h0, const int32_t* env, int32_t S,
+                                  const int32_t* env_episode, int32_t oldest, int32_t count, int32_t n, float gamma,
+                                  float* s, float* s_next, float* a_out, float* r_out, int32_t* steps,
+                                  float* discount, hipStream_t stream) {
+    return replay_gather_nstep(series, T, N, F, W, days, actions, rewards, H, B, h0, env, S, env_episode, true,
+                               oldest, count, n, gamma, s, s_next, a_out, r_out, steps, discount, stream);
+}
+
+static int replay_gather_seq(const float* series, int32_t T, int32_t N, int32_t F, int32_t W, const int32_t* days,
+                             const float* actions, const float* rewards, int32_t H, int32_t B, const int32_t* h0,
+                             const int32_t* env, int32_t S, const int32_t* ids, bool per_env, int32_t oldest,
+                             int32_t count, int32_t L, int32_t time_major, float* x, float* a_out, float* r_out,
+                             int32_t* length, hipStream_t stream) {
     if (!series || !days || !actions || !rewards || !h0 || !env || !x || !a_out || !r_out || !length || T < 1 ||
         N < 1 || F < 2 || W < 1 || H < W + 1 || B < 1 || S < 1 || L < 1 || count < 0 || count > H || oldest < 0 ||
         oldest >= H)
         return PMENV_ERR_ARG;
-    const NstepRing rg{row_episode, oldest, count, L, 1.0};
+    const NstepRing rg{ids, oldest, count, L, 1.0, ids && per_env ? B : 1, ids && per_env ? 1 : 0};
     int policy = -1, lc_knob = 0;
     pmenv_tools::replay_seq_knobs(&policy, &lc_knob);
     const ReplayPlan plan =
@@ -1500,8 +1524,9 @@ int pmenv_replay_gather_seq(const float* series, int32_t T, int32_t N, int32_t F
     case kReplayF5p:
         with_const<2, 4, 8, 12>(plan.ppt, [&](auto ppt) {
             with_const<16, 2, 0>(plan.policy, [&](auto nt) {
-                replay_seq_f5p_kernel<decltype(ppt)::value, decltype(nt)::value>
-                    <<<plan.grid_x, plan.block, plan.lds_bytes, stream>>>(
+                constexpr int kPpt = decltype(ppt)::value, kNt = decltype(nt)::value;
+                auto* kernel = ids && per_env ? replay_seq_f5p_env_kernel<kPpt, kNt> : replay_seq_f5p_kernel<kPpt, kNt>;
+                kernel<<<plan.grid_x, plan.block, plan.lds_bytes, stream>>>(
                         series, T, N, W, days, actions, rewards, H, B, h0, env, S, rg, plan.Lc, plan.nc, time_major,
                         x, a_out, r_out, length, plan.R, make_fastdiv((uint32_t)plan.R),
                         make_fastdiv((uint32_t)(W * F)), make_fastdiv((uint32_t)plan.nc),
@@ -1516,6 +1541,55 @@ int pmenv_replay_gather_seq(const float* series, int32_t T, int32_t N, int32_t F
         break;
     default: return PMENV_ERR_ARG;                         // more workgroups than a grid holds
     }
+    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
+int pmenv_replay_gather_seq(const float* series, int32_t T, int32_t N, int32_t F, int32_t W, const int32_t* days,
+                            const float* actions, const float* rewards, int32_t H, int32_t B, const int32_t* h0,
+                            const int32_t* env, int32_t S, const int32_t* row_episode, int32_t oldest, int32_t count,
+                            int32_t L, int32_t time_major, float* x, float* a_out, float* r_out, int32_t* length,
+                            hipStream_t stream) {
+    return replay_gather_seq(series, T, N, F, W, days, actions, rewards, H, B, h0, env, S, row_episode, false, oldest,
+                             count, L, time_major, x, a_out, r_out, length, stream);
+}
+
+int pmenv_replay_gather_seq_env(const float* series, int32_t T, int32_t N, int32_t F, int32_t W, const int32_t* days,
+                                const float* actions, const float* rewards, int32_t H, int32_t B, const int32_t* h0,
+                                const int32_t* env, int32_t S, const int32_t* env_episode, int32_t oldest,
+                                int32_t count, int32_t L, int32_t time_major, float* x, float* a_out, float* r_out,
+                                int32_t* length, hipStream_t stream) {
+    return replay_gather_seq(series, T, N, F, W, days, actions, rewards, H, B, h0, env, S, env_episode, true, oldest,
+                             count, L, time_major, x, a_out, r_out, length, stream);
+}
+
+// ---- the valid (start, env) pairs of a per-env replay (replay_valid.h)
+int pmenv_replay_valid_build(const int32_t* env_episode, int32_t H, int32_t B, int32_t oldest, int32_t count,
+                             int32_t need, uint64_t* bits, int64_t* rowsum, hipStream_t stream) {
+    if (!env_episode || !rowsum || H < 1 || B < 1 || oldest < 0 || oldest >= H || count < 0 || count > H || need < 1)
+        return PMENV_ERR_ARG;
+    const int span = count > need ? count - need : 0;
+    if (span > 0 && !bits) return PMENV_ERR_ARG;
+    if (((uintptr_t)bits | (uintptr_t)rowsum) & 7u) return PMENV_ERR_ALIGN;
+    const int WB = (B + 63) / 64;
+    if (span > 0) {
+        int waves = (WB + kValidWordsPerWave - 1) / kValidWordsPerWave;
+        waves = waves < 1 ? 1 : waves > 16 ? 16 : waves;
+        valid_bits_kernel<<<(unsigned)span, 64 * waves, 0, stream>>>(env_episode, H, B, oldest, need, WB,
+                                                                     (unsigned long long*)bits, (long long*)rowsum);
+    }
+    valid_scan_kernel<<<1, 1024, 0, stream>>>((long long*)rowsum, span);
+    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
+int pmenv_replay_valid_select(const uint64_t* bits, const int64_t* rowsum, int32_t H, int32_t B, int32_t oldest,
+                              int32_t span, const double* u, int32_t S, int32_t* h0, int32_t* env,
+                              hipStream_t stream) {
+    if (!rowsum || !u || !h0 || !env || H < 1 || B < 1 || oldest < 0 || oldest >= H || span < 0 || span > H ||
+        S < 1 || (span > 0 && !bits))
+        return PMENV_ERR_ARG;
+    if (((uintptr_t)bits | (uintptr_t)rowsum | (uintptr_t)u) & 7u) return PMENV_ERR_ALIGN;
+    valid_select_kernel<<<(unsigned)((S + 3) / 4), 256, 0, stream>>>(
+        (const unsigned long long*)bits, (const long long*)rowsum, H, B, oldest, span, u, S, h0, env);
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
 
@@ -1538,8 +1612,9 @@ int pmenv_prio_init(void* tree, int64_t leaves, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
 
-int pmenv_prio_fill(void* tree, int64_t leaves, int64_t close_first, int64_t open_first, int64_t n,
-                    hipStream_t stream) {
+// ep_first / ep_last: pmenv_prio_fill_env's mask of the open range (nullptr: every leaf of it opens)
+static int prio_fill(void* tree, int64_t leaves, int64_t close_first, int64_t open_first, int64_t n,
+                     const int32_t* ep_first, const int32_t* ep_last, hipStream_t stream) {
     if (!prio_tree_ok(tree, leaves) || n < 0) return PMENV_ERR_ARG;
     if ((uintptr_t)tree & 7u) return PMENV_ERR_ALIGN;
     const int64_t c0 = close_first < 0 ? -1 : close_first, o0 = open_first < 0 ? -1 : open_first;
@@ -1554,9 +1629,21 @@ int pmenv_prio_fill(void* tree, int64_t leaves, int64_t close_first, int64_t ope
         const int64_t oc = o0 < 0 ? 0 : ((o0 + n - 1) >> sh) - (o0 >> sh) + 1;
         prio_fill_kernel<<<(unsigned)((cc + oc + 3) / 4), 256, 0, stream>>>(
             (const float*)base, (float*)(base + t.off[0]), (const double*)(base + t.off[k - 1]),
-            (double*)(base + t.off[k]), leaves, c0, o0, n, sh);
+            (double*)(base + t.off[k]), leaves, c0, o0, n, sh, k == 1 ? ep_first : nullptr,
+            k == 1 ? ep_last : nullptr);
     }
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
+int pmenv_prio_fill(void* tree, int64_t leaves, int64_t close_first, int64_t open_first, int64_t n,
+                    hipStream_t stream) {
+    return prio_fill(tree, leaves, close_first, open_first, n, nullptr, nullptr, stream);
+}
+
+int pmenv_prio_fill_env(void* tree, int64_t leaves, int64_t close_first, int64_t open_first, int64_t n,
+                        const int32_t* ep_first, const int32_t* ep_last, hipStream_t stream) {
+    if (open_first >= 0 && (!ep_first || !ep_last)) return PMENV_ERR_ARG;
+    return prio_fill(tree, leaves, close_first, open_first, n, ep_first, ep_last, stream);
 }
 
 int pmenv_prio_sample(const void* tree, int64_t leaves, int32_t B, const double* u, int32_t S, float beta,

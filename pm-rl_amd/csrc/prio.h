@@ -72,10 +72,12 @@ __global__ void __launch_bounds__(256) prio_init_kernel(unsigned long long* word
 // One wave per touched node of level k (shift = 6k). Level 1 also writes the leaves: a lane
 // whose leaf lies in the close range stores 0, in the open range the maximum. Every wave
 // applies both ranges, so two waves that meet in one node (small n) write the same bits.
-// children: the leaves (k = 1) or level k - 1.
+// children: the leaves (k = 1) or level k - 1. ep_first / ep_last [n] (pmenv_prio_fill_env, level 1 only;
+// nullptr: no mask): leaf o0 + i opens only where ep_first[i] == ep_last[i], the envs whose
+// window lies in one episode; the others keep the 0 their row's close left.
 __global__ void __launch_bounds__(256)
 prio_fill_kernel(const float* hdr, float* leaves, const double* children, double* nodes, int64_t leaf_count,
-                 int64_t c0, int64_t o0, int64_t n, int shift) {
+                 int64_t c0, int64_t o0, int64_t n, int shift, const int32_t* ep_first, const int32_t* ep_last) {
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t cf = c0 >> shift, cc = c0 < 0 ? 0 : ((c0 + n - 1) >> shift) - cf + 1;
@@ -88,7 +90,8 @@ prio_fill_kernel(const float* hdr, float* leaves, const double* children, double
         float x = leaves[i];                               // padded: in bounds
         if (i < leaf_count) {
             if (c0 >= 0 && i >= c0 && i < c0 + n) leaves[i] = x = 0.0f;
-            if (o0 >= 0 && i >= o0 && i < o0 + n) leaves[i] = x = hdr[0];
+            if (o0 >= 0 && i >= o0 && i < o0 + n && (!ep_first || ep_first[i - o0] == ep_last[i - o0]))
+                leaves[i] = x = hdr[0];
         }
         v = (double)x;
     } else {

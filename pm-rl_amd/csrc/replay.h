@@ -584,10 +584,23 @@ __global__ __launch_bounds__(256) void replay_gather_f5p_kernel(const float* ser
 // st .. st+k+W share one episode iff the last one carries the first one's id.
 
 struct NstepRing {
-    const int32_t* row_ep;   // [H] episode id per ring row, nullptr = one episode
+    const int32_t* row_ep;   // episode id of ring row h for env b at [h * stride_h + b * stride_b], nullptr = one episode
     int oldest, count, n;
     double gamma;
+    int stride_h, stride_b;  // (1, 0): one id per row [H], the envs in lockstep; (B, 1): one per (row, env) [H, B]
 };
+// How a kernel addresses the ids. The f5p kernels are built once per layout — the lockstep
+// instantiation reads ids[h], the code it had before there was a second layout, and the
+// *_env_kernel one reads ids[h * B + b] — because the runtime strides cost the lockstep
+// gathers 1-3 % at config 3; the other forms take the strides.
+enum { kEpRow = 0, kEpEnv = 1, kEpStrided = 2 };
+template <int MODE = kEpStrided>
+__device__ __forceinline__ int ring_ep(const NstepRing& rg, const int32_t* __restrict__ ids, int h, int b) {
+    if constexpr (MODE == kEpRow) return ids[h];
+    // one 32 x 32 -> 64-bit multiply-add (stride_b is 0 or 1: b * stride_b < B)
+    if constexpr (MODE == kEpEnv) return ids[(uint64_t)(uint32_t)h * (uint32_t)rg.stride_h + (uint32_t)b];
+    return ids[(uint64_t)(uint32_t)h * (uint32_t)rg.stride_h + (uint32_t)b * (uint32_t)rg.stride_b];
+}
 
 // the cap nn of m from the recorded rows alone, and the episode ids that decide
 // whether it holds: E of row h, far of the last row of start st+nn-1
@@ -604,20 +617,23 @@ __device__ __forceinline__ int nstep_last_row(int H, int W, int h, int k) {   //
 }
 // m from E, far: nn when the farthest window still lies in the episode (two loads, one
 // round trip), else the boundary by bisection — start st is valid, start st+nn-1 is not
-__device__ __forceinline__ int nstep_finish(const NstepRing& rg, int H, int W, int h, int nn, int E, int far) {
+template <int MODE = kEpStrided>
+__device__ __forceinline__ int nstep_finish(const NstepRing& rg, int H, int W, int h, int b, int nn, int E,
+                                            int far) {
     if (far == E) return nn;
     int lo = 1, hi = nn;
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
-        if (rg.row_ep[nstep_last_row(H, W, h, mid)] == E) lo = mid;
+        if (ring_ep<MODE>(rg, rg.row_ep, nstep_last_row(H, W, h, mid), b) == E) lo = mid;
         else hi = mid;
     }
     return lo;
 }
-__device__ __forceinline__ int nstep_count(const NstepRing& rg, int H, int W, int h) {
+__device__ __forceinline__ int nstep_count(const NstepRing& rg, int H, int W, int h, int b) {
     const int nn = nstep_cap(rg, H, W, h);
     if (!rg.row_ep || nn == 1) return nn;
-    return nstep_finish(rg, H, W, h, nn, rg.row_ep[h], rg.row_ep[nstep_last_row(H, W, h, nn)]);
+    return nstep_finish(rg, H, W, h, b, nn, ring_ep(rg, rg.row_ep, h, b),
+                        ring_ep(rg, rg.row_ep, nstep_last_row(H, W, h, nn), b));
 }
 
 // R and gamma^m by one thread: acc = r_k + gamma * acc from the last term (td3.py:94-96)
@@ -673,7 +689,7 @@ static __global__ void replay_nstep_kernel(const float* series, int T, int N, in
         const int ha = (h0[j] + W) % H;
         a_out[i] = actions[((size_t)ha * B + b) * N + n];
         if (n == 0) {
-            const int m = nstep_count(rg, H, W, h0[j]);
+            const int m = nstep_count(rg, H, W, h0[j], b);
             steps[j] = m;
             nstep_fold_serial(rewards, H, B, b, (h0[j] + W - 1) % H, m, rg.gamma, r_out + j, discount + j);
         }
@@ -685,7 +701,7 @@ static __global__ void replay_nstep_kernel(const float* series, int T, int N, in
     rem -= n * W * F;
     const int t = rem / F, f = rem - t * F;
     const int b = env[j], hj = h0[j];
-    const int m = nstep_count(rg, H, W, hj);
+    const int m = nstep_count(rg, H, W, hj, b);
     float v, vn;
     if (f < Fm) {
         const int d = days[(size_t)((hj + W - 1) % H) * B + b] - (W - 1) + t;           // s: the window of h0
@@ -715,7 +731,7 @@ static __global__ __launch_bounds__(256) void replay_nstep_lds_kernel(const floa
     const int j = blockIdx.x, tid = threadIdx.x;
     const int b = env[j], hj = h0[j];
     const int Fm = F - 1;
-    const int m = nstep_count(rg, H, W, hj);                     // uniform: one sample per workgroup
+    const int m = nstep_count(rg, H, W, hj, b);                     // uniform: one sample per workgroup
     const float rw = tid < min(m, 64) ? rewards[(size_t)((hj + W - 1 + tid) % H) * B + b] : 0.0f;
     const int dA = days[(size_t)((hj + W - 1) % H) * B + b] - (W - 1);
     const int dB = days[(size_t)((hj + m + W - 2) % H) * B + b] + 1 - (W - 1);
@@ -784,17 +800,16 @@ static __global__ __launch_bounds__(256) void replay_nstep_lds_kernel(const floa
 // pass, its first 64 rewards in wave 0 — go out once the current image is in LDS, before
 // the write-out; wave 0 folds the current sample's rewards just before it issues them. The index chain runs three samples ahead, one memory level a sample:
 // env / h0, then the day of s with the two episode ids that decide m, then the day of s'.
-template <int PPT, int NT>
-__global__ __launch_bounds__(256) void replay_nstep_f5p_kernel(const float* __restrict__ series, int T, int N, int W,
-                                                               const int32_t* __restrict__ days,
-                                                               const float* __restrict__ actions,
-                                                               const float* __restrict__ rewards, int H, int B,
-                                                               const int32_t* __restrict__ h0,
-                                                               const int32_t* __restrict__ env, int S,
-                                                               NstepRing rg, int D, float* s, float* s_next,
-                                                               float* a_out, float* r_out, int32_t* steps,
-                                                               float* discount, int R, FastDiv div_r,
-                                                               FastDiv div_wf) {
+template <int PPT, int NT, int MODE>
+__device__ __forceinline__ void replay_nstep_f5p_body(const float* __restrict__ series, int T, int N, int W,
+                                                      const int32_t* __restrict__ days,
+                                                      const float* __restrict__ actions,
+                                                      const float* __restrict__ rewards, int H, int B,
+                                                      const int32_t* __restrict__ h0,
+                                                      const int32_t* __restrict__ env, int S, NstepRing rg, int D,
+                                                      float* s, float* s_next, float* a_out, float* r_out,
+                                                      int32_t* steps, float* discount, int R, FastDiv div_r,
+                                                      FastDiv div_wf) {
     constexpr int F = 5;
     extern __shared__ __attribute__((aligned(16))) float ext[];
     const int tid = threadIdx.x;
@@ -840,11 +855,13 @@ __global__ __launch_bounds__(256) void replay_nstep_f5p_kernel(const float* __re
     bool v1 = j + G < S, v2 = j + 2 * G < S, v3 = j + 3 * G < S;
     auto level2 = [&](int bb, int hh, int& nn, int& E, int& far, int& dA) {    // three loads, no branch
         nn = nstep_cap(rg, H, W, hh);
-        E = epp[hh];
-        far = epp[nstep_last_row(H, W, hh, nn)];
+        E = ring_ep<MODE>(rg, epp, hh, bb);
+        far = ring_ep<MODE>(rg, epp, nstep_last_row(H, W, hh, nn), bb);
         dA = day_at(bb, hh + W - 1) - (W - 1);
     };
-    auto finish = [&](int hh, int nn, int E, int far) { return has_ep ? nstep_finish(rg, H, W, hh, nn, E, far) : nn; };
+    auto finish = [&](int bb, int hh, int nn, int E, int far) {
+        return has_ep ? nstep_finish<MODE>(rg, H, W, hh, bb, nn, E, far) : nn;
+    };
     auto level3 = [&](int bb, int hh, int mm) { return day_at(bb, hh + mm + W - 2) + 1 - (W - 1); };
     bc = env[j]; hc = h0[j];
     if (v1) { b1 = env[j + G]; h1 = h0[j + G]; }
@@ -853,11 +870,11 @@ __global__ __launch_bounds__(256) void replay_nstep_f5p_kernel(const float* __re
     {
         int nn, E, far;
         level2(bc, hc, nn, E, far, dAc);
-        mc = finish(hc, nn, E, far);
+        mc = finish(bc, hc, nn, E, far);
         dBc = level3(bc, hc, mc);
         if (v1) {
             level2(b1, h1, nn, E, far, dA1);
-            m1 = finish(h1, nn, E, far);
+            m1 = finish(b1, h1, nn, E, far);
             dB1 = level3(b1, h1, m1);
         }
         if (v2) level2(b2, h2, nn2, E2, far2, dA2);
@@ -945,7 +962,7 @@ __global__ __launch_bounds__(256) void replay_nstep_f5p_kernel(const float* __re
         // round trip covers them
         const int j4 = j + 4 * G;
         const bool v4 = j4 < S;
-        const int m2 = finish(h2, nn2, E2, far2);
+        const int m2 = finish(b2, h2, nn2, E2, far2);
         const int dB2 = level3(b2, h2, m2);
         int nn3, E3, far3, dA3;
         level2(b3, h3, nn3, E3, far3, dA3);
@@ -960,6 +977,26 @@ __global__ __launch_bounds__(256) void replay_nstep_f5p_kernel(const float* __re
         pass = (dBc - dAc == mc && mc <= D - W) ? 0 : 1;
     }
 }
+
+#define PMENV_NSTEP_F5P_ARGS                                                                                         \
+    const float *__restrict__ series, int T, int N, int W, const int32_t *__restrict__ days,                        \
+        const float *__restrict__ actions, const float *__restrict__ rewards, int H, int B,                         \
+        const int32_t *__restrict__ h0, const int32_t *__restrict__ env, int S, NstepRing rg, int D, float *s,      \
+        float *s_next, float *a_out, float *r_out, int32_t *steps, float *discount, int R, FastDiv div_r,           \
+        FastDiv div_wf
+// one id per ring row (rg.row_ep [H], or nullptr)
+template <int PPT, int NT>
+__global__ __launch_bounds__(256) void replay_nstep_f5p_kernel(PMENV_NSTEP_F5P_ARGS) {
+    replay_nstep_f5p_body<PPT, NT, kEpRow>(series, T, N, W, days, actions, rewards, H, B, h0, env, S, rg, D, s,
+                                           s_next, a_out, r_out, steps, discount, R, div_r, div_wf);
+}
+// one id per (ring row, env) (rg.row_ep [H, B], rg.stride_h = B)
+template <int PPT, int NT>
+__global__ __launch_bounds__(256) void replay_nstep_f5p_env_kernel(PMENV_NSTEP_F5P_ARGS) {
+    replay_nstep_f5p_body<PPT, NT, kEpEnv>(series, T, N, W, days, actions, rewards, H, B, h0, env, S, rg, D, s,
+                                           s_next, a_out, r_out, steps, discount, R, div_r, div_wf);
+}
+#undef PMENV_NSTEP_F5P_ARGS
 
 // ---------------------------------------------------------------- sequence samples
 // agent/dreamer/dreamer.py:77-80 trains its world model on sequences of consecutive
@@ -989,7 +1026,7 @@ static __global__ void replay_seq_kernel(const float* series, int T, int N, int 
         int j, t;
         slot(e, j, t);
         const int b = env[j], hj = h0[j];
-        const int m = nstep_count(rg, H, W, hj);
+        const int m = nstep_count(rg, H, W, hj, b);
         const bool live = t < m;                        // t < m <= H: the rows below stay under 3H
         a_out[i] = live ? actions[((size_t)ring_wrap(ring_wrap(hj + W + t, H), H) * B + b) * N + n] : 0.0f;
         if (n == 0) {
@@ -1007,7 +1044,7 @@ static __global__ void replay_seq_kernel(const float* series, int T, int N, int 
     const int p = rem / F, f = rem - p * F;
     const int b = env[j], hj = h0[j];
     float v = 0.0f;
-    if (t < nstep_count(rg, H, W, hj)) {
+    if (t < nstep_count(rg, H, W, hj, b)) {
         const int ht = ring_wrap(hj + t, H);            // the element's one-step start
         if (f < Fm) {
             const int d = days[(size_t)ring_wrap(ht + W - 1, H) * B + b] - (W - 1) + p;
@@ -1034,16 +1071,16 @@ static __global__ void replay_seq_kernel(const float* series, int T, int N, int 
 // it the episode ids that give m and the chunk's day indices. A chunk whose days do not
 // advance by one a row (a caller's own ring) is staged and written element by element.
 // NT: cache-policy bits of the window stores (0 plain, 2 nt, 16 sc1).
-template <int PPT, int NT>
-__global__ __launch_bounds__(256) void replay_seq_f5p_kernel(const float* __restrict__ series, int T, int N, int W,
-                                                             const int32_t* __restrict__ days,
-                                                             const float* __restrict__ actions,
-                                                             const float* __restrict__ rewards, int H, int B,
-                                                             const int32_t* __restrict__ h0,
-                                                             const int32_t* __restrict__ env, int S, NstepRing rg,
-                                                             int Lc, int nc, int time_major, float* x, float* a_out,
-                                                             float* r_out, int32_t* length, int R, FastDiv div_r,
-                                                             FastDiv div_wf, FastDiv div_nc, FastDiv div_gy) {
+template <int PPT, int NT, int MODE>
+__device__ __forceinline__ void replay_seq_f5p_body(const float* __restrict__ series, int T, int N, int W,
+                                                    const int32_t* __restrict__ days,
+                                                    const float* __restrict__ actions,
+                                                    const float* __restrict__ rewards, int H, int B,
+                                                    const int32_t* __restrict__ h0,
+                                                    const int32_t* __restrict__ env, int S, NstepRing rg, int Lc,
+                                                    int nc, int time_major, float* x, float* a_out, float* r_out,
+                                                    int32_t* length, int R, FastDiv div_r, FastDiv div_wf,
+                                                    FastDiv div_nc, FastDiv div_gy) {
     constexpr int F = 5;
     extern __shared__ __attribute__((aligned(16))) float ext[];
     int* flg = reinterpret_cast<int*>(ext);                // [4] each wave's verdict on a chunk's days
@@ -1076,10 +1113,11 @@ __global__ __launch_bounds__(256) void replay_seq_f5p_kernel(const float* __rest
         const int tc = min(it.t0, nn - 1);                 // a chunk past nn is empty: any rows do
         const int span = min(Lc, nn - tc);
         const int row0 = ring_wrap(ring_wrap(it.h + W - 1, H) + tc, H);
-        const int E = epp[it.h], far = epp[nstep_last_row(H, W, it.h, nn)];
+        const int E = ring_ep<MODE>(rg, epp, it.h, it.b);
+        const int far = ring_ep<MODE>(rg, epp, nstep_last_row(H, W, it.h, nn), it.b);
         const int dfirst = days[(size_t)row0 * B + it.b];
         const int dmine = days[(size_t)ring_wrap(row0 + min(tid, span - 1), H) * B + it.b];
-        it.m = has_ep && nn > 1 ? nstep_finish(rg, H, W, it.h, nn, E, far) : nn;
+        it.m = has_ep && nn > 1 ? nstep_finish<MODE>(rg, H, W, it.h, it.b, nn, E, far) : nn;
         it.cnt = max(0, min(Lc, it.m - it.t0));
         it.dA = dfirst - (W - 1);
         const int ok = __all(tid >= it.cnt || dmine - dfirst == tid);
@@ -1208,5 +1246,25 @@ __global__ __launch_bounds__(256) void replay_seq_f5p_kernel(const float* __rest
         n2 = n3; v2 = v3; i2 = i3;
     }
 }
+
+#define PMENV_SEQ_F5P_ARGS                                                                                           \
+    const float *__restrict__ series, int T, int N, int W, const int32_t *__restrict__ days,                        \
+        const float *__restrict__ actions, const float *__restrict__ rewards, int H, int B,                         \
+        const int32_t *__restrict__ h0, const int32_t *__restrict__ env, int S, NstepRing rg, int Lc, int nc,       \
+        int time_major, float *x, float *a_out, float *r_out, int32_t *length, int R, FastDiv div_r,                \
+        FastDiv div_wf, FastDiv div_nc, FastDiv div_gy
+// one id per ring row (rg.row_ep [H], or nullptr)
+template <int PPT, int NT>
+__global__ __launch_bounds__(256) void replay_seq_f5p_kernel(PMENV_SEQ_F5P_ARGS) {
+    replay_seq_f5p_body<PPT, NT, kEpRow>(series, T, N, W, days, actions, rewards, H, B, h0, env, S, rg, Lc, nc,
+                                         time_major, x, a_out, r_out, length, R, div_r, div_wf, div_nc, div_gy);
+}
+// one id per (ring row, env) (rg.row_ep [H, B], rg.stride_h = B)
+template <int PPT, int NT>
+__global__ __launch_bounds__(256) void replay_seq_f5p_env_kernel(PMENV_SEQ_F5P_ARGS) {
+    replay_seq_f5p_body<PPT, NT, kEpEnv>(series, T, N, W, days, actions, rewards, H, B, h0, env, S, rg, Lc, nc,
+                                         time_major, x, a_out, r_out, length, R, div_r, div_wf, div_nc, div_gy);
+}
+#undef PMENV_SEQ_F5P_ARGS
 
 }  // namespace pmenv_dev

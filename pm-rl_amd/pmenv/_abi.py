@@ -17,7 +17,9 @@ PMENV_ABI_VERSION = 4   # 2: pmenv_window_written / pmenv_state_written; cfg def
                         # 3: pmenv_step_host / pmenv_reset_host
                         # 4: pmenv_replay_gather_nstep
                         #    (pmenv_replay_gather_seq, pmenv_prio_*, pmenv_restart_days and
-                        #    pmenv_replay_path added under 4: load() names a missing symbol)
+                        #    pmenv_replay_path added under 4: load() names a missing symbol;
+                        #    pmenv_replay_valid_build / _select, pmenv_replay_gather_nstep_env /
+                        #    _seq_env and pmenv_prio_fill_env likewise)
 
 # enums (include/pmenv.h)
 REWARD_KINDS = {"log_returns": 0, "returns": 1, "sharpe_ratio": 2, "diff_sharpe": 3}
@@ -103,10 +105,19 @@ SIGNATURES = [
     ("pmenv_replay_gather_seq", ctypes.c_int,
      [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, _I32,
       _P, _P, _P, _P, _P]),
+    ("pmenv_replay_valid_build", ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    ("pmenv_replay_valid_select", ctypes.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _I32, _P, _P, _P]),
+    ("pmenv_replay_gather_nstep_env", ctypes.c_int,
+     [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, _F,
+      _P, _P, _P, _P, _P, _P, _P]),
+    ("pmenv_replay_gather_seq_env", ctypes.c_int,
+     [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _I32, _I32,
+      _P, _P, _P, _P, _P]),
     ("pmenv_replay_path", ctypes.c_char_p, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
     ("pmenv_prio_tree_bytes", _SZ, [_I64]),
     ("pmenv_prio_init", ctypes.c_int, [_P, _I64, _P]),
     ("pmenv_prio_fill", ctypes.c_int, [_P, _I64, _I64, _I64, _I64, _P]),
+    ("pmenv_prio_fill_env", ctypes.c_int, [_P, _I64, _I64, _I64, _I64, _P, _P, _P]),
     ("pmenv_prio_sample", ctypes.c_int, [_P, _I64, _I32, _P, _I32, _F, _P, _P, _P, _P, _P]),
     ("pmenv_prio_update", ctypes.c_int, [_P, _I64, _P, _P, _I32, _F, _F, _P]),
     ("pmenv_rollout_gather", ctypes.c_int,

@@ -19,6 +19,8 @@ and the evaluation metrics all on device.
     update_priorities(idxs, td_error)            td = update(s, a, r, s_, weights);     agent/td3/td3.py:118-144)
       (agent/td3/td3.py:118,144)                 replay.update_priorities(leaf, td)
     metrics.write()                      :110    trajectory_metrics(...)               (HIP reductions)
+    (one env walks the series to its end, :60-86)  collect_episodes(ep, obs, steps)      (episodes=True: every env ends
+                                                 replay.add(d, a, r, done=done)         and restarts on its own)
 
 Every env trades the one HBM-resident series (pmenv.data.MarketSeries) from its own
 start day: the step reads day[b]'s bar straight from the series (no per-step host
@@ -32,7 +34,8 @@ from .replay import DeviceReplay, trajectory_metrics
 
 class OffPolicy:
     def __init__(self, env, series, capacity, act=None, update=None, batch_size=256, generator=None,
-                 n_step=1, gamma=0.997, seq_len=0, prioritized=False, alpha=0.6, beta=0.4, beta_increment=0.0):
+                 n_step=1, gamma=0.997, seq_len=0, prioritized=False, alpha=0.6, beta=0.4, beta_increment=0.0,
+                 episodes=False):
         """env: a pmenv.TradingEnv over B envs; series: pmenv.data.MarketSeries [T, N, F-1];
         capacity: replay steps kept per env (buffer.py's ring); act(obs [B, N, W, F]) ->
         [B, N] weights; update(s, a, r, s_) -> anything (one agent update). n_step > 1
@@ -45,7 +48,10 @@ class OffPolicy:
         prioritized (agent/td3/td3.py:39,118-144): batches are drawn by priority and
         update(s, a, r, s_, weights) -> td_error [S] — with n_step > 1 update(s, a, R, s_,
         discount, weights) — whose result goes to replay.update_priorities; weights [S] are
-        the importance weights of the critic loss (:126,143). Not with seq_len > 0."""
+        the importance weights of the critic loss (:126,143). Not with seq_len > 0.
+        episodes: the envs end and restart on their own (`collect_episodes` over a
+        pmenv.episodes.Episodes); the replay keeps an episode id per (row, env), so no sample
+        of any kind spans an env's restart."""
         if n_step < 1 or not 0.0 < gamma <= 1.0:
             raise ValueError("n_step must be >= 1 and gamma in (0, 1]")
         if seq_len < 0 or (seq_len > 0 and n_step > 1):
@@ -58,7 +64,8 @@ class OffPolicy:
         self.env, self.series = env, series
         self.B, self.N, self.W = cfg.num_envs, cfg.num_assets, cfg.window
         self.replay = DeviceReplay(self.B, self.N, self.W, capacity, series, cfg.features, prioritized=prioritized,
-                                   alpha=alpha, beta=beta, beta_increment=beta_increment)
+                                   alpha=alpha, beta=beta, beta_increment=beta_increment, per_env=episodes)
+        self.episodes = bool(episodes)
         self.act_fn, self.update_fn = act, update
         self.batch_size = batch_size
         self.generator = generator
@@ -94,6 +101,29 @@ class OffPolicy:
             rewards.append(r)
             day = day + 1
         return torch.stack(rewards), obs
+
+    def collect_episodes(self, ep, obs, steps, random=False):
+        """The continuous loop of pmenv.episodes.collect with every step recorded: act ->
+        env.step(series=, day=ep.next_day) -> env.restart -> replay.add(.., done=). ep: the
+        Episodes of the envs; obs: their windows (series.initial_window(ep.start, W), reset),
+        advanced in place. Returns (rewards [steps, B] f32, dones [steps, B] bool)."""
+        if not self.episodes:
+            raise ValueError("collect_episodes needs OffPolicy(episodes=True)")
+        rewards = torch.empty(steps, self.B, dtype=torch.float32, device=self.env.device)
+        dones = torch.empty(steps, self.B, dtype=torch.uint8, device=self.env.device)
+        for t in range(steps):
+            if random or self.act_fn is None:
+                a = self._random_action()
+            else:
+                with torch.no_grad():
+                    a = self.act_fn(obs)
+            d = ep.next_day - 1                   # the day of the window the action is taken on
+            r, _ = self.env.step(a, obs, series=self.series, day=ep.next_day)
+            done = self.env.restart(obs, ep)      # rewrites next_day
+            self.replay.add(d, a, r, done=done)
+            rewards[t] = r
+            dones[t] = done
+        return rewards, dones.bool()
 
     def update(self, steps):
         """_update_off_policy (off_policy.py:88-94): `steps` sampled batches into update()."""

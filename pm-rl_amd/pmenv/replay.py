@@ -9,6 +9,9 @@ dataset. `sample_nstep` folds n-step returns at sample time (agent/td3/td3.py:85
 `sample_sequences` serves sequences of consecutive steps (agent/dreamer/dreamer.py:77-80).
 `prioritized=True` keeps a resident sum tree over the one-step starts (td3.py:39,118,144;
 Schaul et al. 2016, proportional variant): `sample_prioritized`, `update_priorities`.
+`per_env=True` keeps an episode id per (ring row, env) on the device, for envs that restart on
+their own (`TradingEnv.restart`): every sampling kind then draws from the valid (start, env)
+pairs of `valid_pairs`, built and drawn from on the device (csrc/replay_valid.h).
 `trajectory_metrics` restates util/eval.py:14-37 (Sharpe, Sortino, max
 drawdown, average turnover) per env on device.
 """
@@ -74,6 +77,50 @@ def sequence_starts(row_episode, oldest, count, W, H, L):
         return range(span)
     chrono = np.roll(ep, -oldest)[:count]                 # rows oldest .. newest
     return np.flatnonzero(chrono[:span] == chrono[W + L - 1:W + L - 1 + span])
+
+
+def valid_pairs(env_episode, oldest, count, need, H):
+    """The valid (st, env) pairs of a per-env ring, int64 [total, 2] in (st ascending, env
+    ascending) order: st an offset from the oldest recorded row, below span = max(count -
+    need, 0), whose rows st .. st + need - 1 share one episode in column env. env_episode
+    [H, B] holds ids that never decrease along the ring for one env, so the first and the
+    last row decide: column b is `valid_starts(env_episode[:, b], ..)` for need = W + 1 and
+    `sequence_starts(.., L)` for need = W + L. No torch, no device: this is the statement
+    pmenv_replay_valid_build / _select are held to (select's k-th pair is row k)."""
+    ep = np.asarray(env_episode)
+    ep = ep.reshape(H, -1)
+    span = max(count - need, 0)
+    chrono = np.roll(ep, -oldest, axis=0)[:count]         # rows oldest .. newest
+    st, env = np.nonzero(chrono[:span] == chrono[need - 1:need - 1 + span])
+    return np.stack([st, env], axis=1).astype(np.int64)
+
+
+def valid_build(env_episode, oldest, count, need, out=None):
+    """pmenv_replay_valid_build for env_episode [H, B] int32 on the device: (bits int64
+    [span, ceil(B / 64)] — the u64 words — , rowsum int64 [span + 1]). out: preallocated
+    (bits, rowsum)."""
+    H, B = env_episode.shape
+    span, WB = max(count - need, 0), (B + 63) // 64
+    if out is None:
+        out = (torch.empty(span, WB, dtype=torch.int64, device=env_episode.device),
+               torch.empty(span + 1, dtype=torch.int64, device=env_episode.device))
+    bits, rowsum = out
+    _abi.check(_abi.load().pmenv_replay_valid_build(_p(env_episode), H, B, oldest, count, need,
+                                                    _p(bits) if span else None, _p(rowsum),
+                                                    _stream(env_episode.device)), None, "pmenv_replay_valid_build")
+    return bits, rowsum
+
+
+def valid_select(bits, rowsum, H, B, oldest, u, out=None):
+    """pmenv_replay_valid_select for targets u [S] f64 on the device: (h0, env) int32 [S]."""
+    S, dev, span = u.numel(), rowsum.device, rowsum.numel() - 1
+    if out is None:
+        out = (torch.empty(S, dtype=torch.int32, device=dev), torch.empty(S, dtype=torch.int32, device=dev))
+    h0, env = out
+    _abi.check(_abi.load().pmenv_replay_valid_select(_p(bits) if span else None, _p(rowsum), H, B, oldest, span,
+                                                     _p(u), S, _p(h0), _p(env), _stream(dev)),
+               None, "pmenv_replay_valid_select")
+    return h0, env
 
 
 def prio_row_events(row_episode, head, count, episode, W, H):
@@ -145,6 +192,14 @@ def prio_fill(tree, leaves, close_first, open_first, n):
                None, "pmenv_prio_fill")
 
 
+def prio_fill_env(tree, leaves, close_first, open_first, n, ep_first, ep_last):
+    """pmenv_prio_fill_env: `prio_fill` whose open range takes only the leaves i with
+    ep_first[i] == ep_last[i] (int32 [n] on the device)."""
+    _abi.check(_abi.load().pmenv_prio_fill_env(_p(tree), leaves, -1 if close_first is None else close_first,
+                                               -1 if open_first is None else open_first, n, _p(ep_first),
+                                               _p(ep_last), _stream(tree.device)), None, "pmenv_prio_fill_env")
+
+
 def prio_sample(tree, leaves, B, u, beta, out=None):
     """pmenv_prio_sample for targets u [S] f64 in [0, 1): (leaf, h0, env int32, weights f32).
     out: the four preallocated outputs (a captured graph's buffers)."""
@@ -166,8 +221,12 @@ def prio_update(tree, leaves, leaf, td, alpha, eps):
 
 class DeviceReplay:
     def __init__(self, num_envs, num_assets, window, capacity, series, features=5, prioritized=False, alpha=0.6,
-                 beta=0.4, beta_increment=0.0, eps=1e-6):
-        """prioritized (agent/td3/td3.py:39 PrioritizedReplayBuffer(buffer_size, alpha, beta,
+                 beta=0.4, beta_increment=0.0, eps=1e-6, per_env=False):
+        """per_env: the envs end their episodes on their own (`add(.., done=)`, the mask
+        `TradingEnv.restart` returns): `env_episode` [H, B] int32 holds an id per (row, env)
+        on the device and every sampling kind draws from the valid (start, env) pairs
+        (`valid_pairs`). Default: the envs record in lockstep, one id per ring row.
+        prioritized (agent/td3/td3.py:39 PrioritizedReplayBuffer(buffer_size, alpha, beta,
         beta_incr)): keep a priority tree over the H * B one-step starts, current after every
         `add`; `sample_prioritized` / `sample_nstep_prioritized` draw from it and
         `update_priorities` feeds the TD errors back. Sequence samples stay uniform: a
@@ -201,6 +260,15 @@ class DeviceReplay:
         self._leaves = capacity * num_envs
         self._row_open = np.zeros(capacity, dtype=bool)   # ring rows whose leaves are open (valid starts), kept by add
         self.tree = prio_tree(self._leaves, dev) if prioritized else None
+        self.per_env = bool(per_env)
+        if self.per_env:
+            # the ids and the id the next row of each env takes live on the device alone
+            self.env_episode = torch.zeros(capacity, num_envs, dtype=torch.int32, device=dev)
+            self._cur = torch.zeros(num_envs, dtype=torch.int32, device=dev)
+            self._adds = 0                # rows recorded so far: never repeats, unlike (head, count) of a full ring
+            self._valid_at = None         # the _adds the cached maps were built at
+            self._valid_maps = {}         # need -> (bits, rowsum, total)
+            self._row_ep = self._row_open = None   # lockstep's host copies: not kept in this mode
 
     def __len__(self):
         return self.count
@@ -209,9 +277,69 @@ class DeviceReplay:
         """Steps added from now on belong to a new episode (the env was reset): no sampled
         window spans the boundary (buffer.py keeps each epoch in its own row)."""
         self.episode += 1
+        if self.per_env:
+            self._cur += 1
 
-    def add(self, day, action, reward):
-        """buffer.py:23-37: one recorded step for every env."""
+    def _add_per_env(self, day, action, reward, done):
+        """`add` with an id per (row, env): plain torch and one tree launch, no sync."""
+        h, H, W, B = self.head, self.H, self.W, self.B
+        self.days[h].copy_(torch.as_tensor(day).reshape(B))
+        self.actions[h].copy_(torch.as_tensor(action).reshape(B, self.N))
+        self.rewards[h].copy_(torch.as_tensor(reward).reshape(B))
+        self.env_episode[h].copy_(self._cur)
+        if done is not None:
+            self._cur += (torch.as_tensor(done).to(self._cur.device).reshape(B) != 0).to(torch.int32)
+        full = self.count == H
+        self._adds += 1                   # the cached valid maps describe the ids before this row
+        self._valid_at, self._valid_maps = None, {}
+        self.head = (h + 1) % H
+        self.count = min(self.count + 1, H)
+        if self.prioritized:
+            # the overwritten row's starts close; the start at offset count' - W - 2, the only
+            # one the new row completes, opens for the envs whose window lies in one episode
+            oldest = (self.head - self.count) % H
+            st = self.count - W - 2
+            close = h * B if full else None
+            if st >= 0:
+                first, last = (oldest + st) % H, (oldest + st + W) % H
+                prio_fill_env(self.tree, self._leaves, close, first * B, B, self.env_episode[first],
+                              self.env_episode[last])
+            elif close is not None:
+                prio_fill(self.tree, self._leaves, close, None, B)
+
+    def _valid(self, need):
+        """The valid-pair map for `need` rows of one episode: (bits, rowsum, total), cached
+        until the next add — `add` drops the maps, and they are keyed by the count of rows ever
+        recorded, since (head, count) of a full ring comes round again every H adds. A rebuild
+        reads the total back: 8 bytes, the only host read."""
+        at = self._adds
+        if self._valid_at != at:
+            self._valid_at, self._valid_maps = at, {}
+        hit = self._valid_maps.get(need)
+        if hit is None:
+            oldest = (self.head - self.count) % self.H
+            bits, rowsum = valid_build(self.env_episode, oldest, self.count, need)
+            hit = self._valid_maps[need] = (bits, rowsum, int(rowsum[-1].item()))
+        return hit
+
+    def _draw(self, need, batch_size, generator, u):
+        """S uniform draws from the valid pairs of `need` (total > 0): (h0, env) int32."""
+        bits, rowsum, _ = self._valid(need)
+        dev = self.days.device
+        if u is None:
+            gdev = generator.device if generator is not None else dev
+            u = torch.rand(batch_size, dtype=torch.float64, generator=generator, device=gdev)
+        u = torch.as_tensor(u, dtype=torch.float64).to(dev).reshape(batch_size).contiguous()
+        return valid_select(bits, rowsum, self.H, self.B, (self.head - self.count) % self.H, u)
+
+    def add(self, day, action, reward, done=None):
+        """buffer.py:23-37: one recorded step for every env. done [B] (per_env only; uint8 or
+        bool, the mask `TradingEnv.restart` returns): env b's episode ended with this step,
+        its next row opens a new one; None: no env ended."""
+        if self.per_env:
+            return self._add_per_env(day, action, reward, done)
+        if done is not None:
+            raise ValueError("done= needs a replay built with per_env=True")
         h = self.head
         if self.prioritized:              # from the state before the add
             close_row, open_row = prio_row_events(self._row_ep, h, self.count, self.episode, self.W, self.H)
@@ -231,12 +359,19 @@ class DeviceReplay:
                 prio_fill(self.tree, self._leaves, None if close_row is None else close_row * self.B,
                           None if open_row is None else open_row * self.B, self.B)
 
-    def indices(self, batch_size, generator=None):
+    def indices(self, batch_size, generator=None, u=None):
         """Random (start, env) pairs with W+1 consecutive recorded steps of one episode
-        (buffer.py:47-51)."""
+        (buffer.py:47-51). per_env: pair floor(u * total) of `valid_pairs(.., W + 1)`, u [S]
+        f64 in [0, 1) drawn with the generator (an explicit u makes the draw exact)."""
         span = self.count - self.W - 1
         if span < 1:
             raise ValueError("not enough recorded steps to sample a window")
+        if self.per_env:
+            if self._valid(self.W + 1)[2] == 0:
+                raise ValueError("no episode holds W + 1 recorded steps")
+            return self._draw(self.W + 1, batch_size, generator, u)
+        if u is not None:
+            raise ValueError("u= needs a replay built with per_env=True")
         # drawn where the generator lives: a CPU generator (reproducible across devices)
         # costs a host->device copy per batch; no generator or a device one stays on the GPU
         dev = self.days.device
@@ -295,6 +430,8 @@ class DeviceReplay:
         if self._row_ep_dirty:
             self._row_ep_dev.copy_(torch.from_numpy(self._row_ep.astype(np.int32)))
             self._row_ep_dirty = False
+        fn, ids = ((lib.pmenv_replay_gather_nstep_env, self.env_episode) if self.per_env else
+                   (lib.pmenv_replay_gather_nstep, self._row_ep_dev))
         s = torch.empty(S, self.N, self.W, self.F, device=dev)
         s2 = torch.empty_like(s)
         a = torch.empty(S, self.N, device=dev)
@@ -304,12 +441,10 @@ class DeviceReplay:
         sb = self.series.bars
         oldest = (self.head - self.count) % self.H
         st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _abi.check(lib.pmenv_replay_gather_nstep(_p(sb), sb.shape[0], self.N, self.F, self.W, _p(self.days),
-                                                 _p(self.actions), _p(self.rewards), self.H, self.B,
-                                                 _p(h0.contiguous()), _p(env.contiguous()), S,
-                                                 _p(self._row_ep_dev), oldest, self.count, int(n_step), float(gamma),
-                                                 _p(s), _p(s2), _p(a), _p(r), _p(steps), _p(disc), st),
-                   None, "pmenv_replay_gather_nstep")
+        _abi.check(fn(_p(sb), sb.shape[0], self.N, self.F, self.W, _p(self.days), _p(self.actions), _p(self.rewards),
+                      self.H, self.B, _p(h0.contiguous()), _p(env.contiguous()), S, _p(ids), oldest, self.count,
+                      int(n_step), float(gamma), _p(s), _p(s2), _p(a), _p(r), _p(steps), _p(disc), st),
+                   None, "pmenv_replay_gather_nstep_env" if self.per_env else "pmenv_replay_gather_nstep")
         return s, a.reshape(S, self.N, 1), r.reshape(S, 1, 1), s2, steps, disc
 
     def sample_nstep(self, batch_size, n_step, gamma=0.997, generator=None):
@@ -328,7 +463,11 @@ class DeviceReplay:
             raise ValueError("the replay was built with prioritized=False")
         if self.count - self.W - 1 < 1:
             raise ValueError("not enough recorded steps to sample a window")
-        if not self._row_open.any():
+        if self.per_env:
+            empty = self._valid(self.W + 1)[2] == 0
+        else:
+            empty = not self._row_open.any()
+        if empty:
             raise ValueError("no episode holds W + 1 recorded steps")
         dev = self.days.device
         if u is None:
@@ -365,15 +504,22 @@ class DeviceReplay:
         prio_update(self.tree, self._leaves, leaf, td, self.alpha, self.eps)
 
 
-    def sequence_indices(self, batch_size, L, generator=None):
+    def sequence_indices(self, batch_size, L, generator=None, u=None):
         """Random (start, env) pairs whose sequences of L consecutive one-step samples are
         full length: W + L recorded rows of one episode (`sequence_starts`). The generator
-        and device rules are those of `indices`."""
+        and device rules are those of `indices`, and so are per_env's draw and u, over
+        `valid_pairs(.., W + L)`."""
         if L < 1:
             raise ValueError("L must be >= 1")
         span = self.count - self.W - L
         if span < 1:
             raise ValueError("no episode holds W + L recorded steps")
+        if self.per_env:
+            if self._valid(self.W + int(L))[2] == 0:
+                raise ValueError("no episode holds W + L recorded steps")
+            return self._draw(self.W + int(L), batch_size, generator, u)
+        if u is not None:
+            raise ValueError("u= needs a replay built with per_env=True")
         dev = self.days.device
         gdev = generator.device if generator is not None else dev
         oldest = (self.head - self.count) % self.H
@@ -410,6 +556,8 @@ class DeviceReplay:
         if self._row_ep_dirty:
             self._row_ep_dev.copy_(torch.from_numpy(self._row_ep.astype(np.int32)))
             self._row_ep_dirty = False
+        fn, ids = ((lib.pmenv_replay_gather_seq_env, self.env_episode) if self.per_env else
+                   (lib.pmenv_replay_gather_seq, self._row_ep_dev))
         lead = (L, S) if time_major else (S, L)
         x = torch.empty(*lead, self.N, self.W, self.F, device=dev)
         a = torch.empty(*lead, self.N, device=dev)
@@ -418,11 +566,10 @@ class DeviceReplay:
         sb = self.series.bars
         oldest = (self.head - self.count) % self.H
         st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _abi.check(lib.pmenv_replay_gather_seq(_p(sb), sb.shape[0], self.N, self.F, self.W, _p(self.days),
-                                               _p(self.actions), _p(self.rewards), self.H, self.B,
-                                               _p(h0.contiguous()), _p(env.contiguous()), S, _p(self._row_ep_dev),
-                                               oldest, self.count, L, 1 if time_major else 0, _p(x), _p(a), _p(r),
-                                               _p(length), st), None, "pmenv_replay_gather_seq")
+        _abi.check(fn(_p(sb), sb.shape[0], self.N, self.F, self.W, _p(self.days), _p(self.actions), _p(self.rewards),
+                      self.H, self.B, _p(h0.contiguous()), _p(env.contiguous()), S, _p(ids), oldest, self.count, L,
+                      1 if time_major else 0, _p(x), _p(a), _p(r), _p(length), st), None,
+                   "pmenv_replay_gather_seq_env" if self.per_env else "pmenv_replay_gather_seq")
         return x, a, r, length
 
     def sample_sequences(self, batch_size, L, generator=None, time_major=True):
