@@ -43,7 +43,8 @@ extern "C" {
  *    episodes on the resident series, likewise; pmenv_replay_path, the sample gathers'
  *    kernel by name, likewise; pmenv_replay_valid_build, pmenv_replay_valid_select,
  *    pmenv_replay_gather_nstep_env, pmenv_replay_gather_seq_env and pmenv_prio_fill_env, the
- *    replay of envs that end their episodes on their own, likewise) */
+ *    replay of envs that end their episodes on their own, likewise; pmenv_rollout_gather_env and
+ *    pmenv_rollout_gather_env_path, the compact rollout of such envs, likewise) */
 #define PMENV_ABI_VERSION 4
 
 /* Opaque HIP stream (identical to HIP's own typedef); NULL = default stream. */
@@ -623,6 +624,39 @@ int pmenv_prio_update(void* tree, int64_t leaves, const int32_t* leaf, const flo
 int pmenv_rollout_gather(const float* series, int32_t T, int32_t N, int32_t F, int32_t W, const int32_t* start,
                          const float* weights, int32_t T_rec, int32_t B, int32_t ring_mode,
                          const int32_t* t_idx, const int32_t* env, int32_t S, float* s, hipStream_t stream);
+
+/* The per-env form of the compact rollout: envs that restart on their own
+ * (pmenv_restart_days) and rollouts that continue from where the last one stopped. For every
+ * buffer row t = 0 .. T_rec and env b two int32 arrays [T_rec + 1, B] describe the window env
+ * b holds after step t:
+ *   first[t, b]    the series day of the window's first day (restart[b] after a restart);
+ *   updates[t, b]  the ring updates since the env's last reset at that moment, 0 for a window
+ *                  a reset or a restart just wrote.
+ * weights is [carry + T_rec, B, N]: the post-drift weights w' of step g (1 <= g <= T_rec) sit
+ * in row carry + g - 1, rows 0 .. carry - 1 hold the w' of the `carry` steps before this
+ * rollout began (carry = 0, or W when a rollout resumes). The lockstep case is
+ * first = start[b] + t, updates = t, carry = 0, and gives pmenv_rollout_gather's bits.
+ * The window (t, b), with u = updates[t, b]:
+ *   market channels f < F-1 read series[first[t, b] + p, n, f], NaN outside the series;
+ *   the weight channel at window position p has chronological position c = p, or, in
+ *   PMENV_RING_STORAGE mode with u >= W-1, c = (p - u - 1) mod W; its episode-local history
+ *   row is r = u + c: r < W-1 reads 0, r == W-1 reads e0 (1 for asset 0, else 0), r > W-1
+ *   reads the w' of step g = t + c - W + 1, weights row carry + t + c - W.
+ * The caller keeps t_idx <= T_rec and updates[t, b] <= t + carry, so that a row r > W-1 lies
+ * in weights (with carry >= W every position has its row, whatever u is: an env that never
+ * restarts may run on across resumed rollouts); a weights row outside [0, carry + T_rec)
+ * reads 0.0f, never memory. The same plan as pmenv_rollout_gather (form,
+ * grid, LDS bytes, store policy) with the kernels rollout_gather_env_tile_kernel /
+ * rollout_gather_env_rows_kernel; enqueues on `stream`, never allocates, frees or
+ * synchronises (capturable). PMENV_ERR_ARG: a NULL pointer, carry < 0, or
+ * pmenv_rollout_gather's shape errors. */
+int pmenv_rollout_gather_env(const float* series, int32_t T, int32_t N, int32_t F, int32_t W,
+                             const int32_t* first, const int32_t* updates, const float* weights, int32_t carry,
+                             int32_t T_rec, int32_t B, int32_t ring_mode, const int32_t* t_idx,
+                             const int32_t* env, int32_t S, float* s, hipStream_t stream);
+/* pmenv_replay_path(PMENV_REPLAY_ROLLOUT, ...)'s string with the per-env kernels' names; "" for
+ * a shape the gather rejects. Host only: launches nothing, touches no device. */
+const char* pmenv_rollout_gather_env_path(int32_t N, int32_t F, int32_t W, int32_t S, int32_t aligned);
 
 /* util/eval.py:14-37 per env over a trajectory: returns [T, B] (simple returns),
  * values [T+1, B] f64, weights [T+1, B, N]; out [B, 5] f64 =

@@ -1709,6 +1709,42 @@ int pmenv_rollout_gather(const float* series, int32_t T, int32_t N, int32_t F, i
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
 
+// the per-env form: the lockstep call's plan (form, grid, LDS bytes, store policy), the env kernels
+int pmenv_rollout_gather_env(const float* series, int32_t T, int32_t N, int32_t F, int32_t W, const int32_t* first,
+                             const int32_t* updates, const float* weights, int32_t carry, int32_t T_rec, int32_t B,
+                             int32_t ring_mode, const int32_t* t_idx, const int32_t* env, int32_t S, float* s,
+                             hipStream_t stream) {
+    if (!series || !first || !updates || !weights || carry < 0 || !t_idx || !env || !s || T < 1 || N < 1 || F < 2 ||
+        W < 1 || T_rec < 0 || B < 1 || S < 1 || ring_mode < 0 || ring_mode > 1)
+        return PMENV_ERR_ARG;
+    const ReplayPlan plan =
+        replay_plan(PMENV_REPLAY_ROLLOUT, N, F, W, 1, S, replay_aligned(s, s, series), device_cus());
+    switch (plan.form) {
+    case kRolloutTile:
+        with_const<16, 2>(plan.policy, [&](auto nt) {
+            rollout_gather_env_tile_kernel<decltype(nt)::value><<<plan.grid_x, plan.block, plan.lds_bytes, stream>>>(
+                series, T, N, W, first, updates, weights, carry, T_rec, B, ring_mode, t_idx, env, s,
+                make_fastdiv((uint32_t)N), make_fastdiv((uint32_t)(W * F)), make_fastdiv((uint32_t)F));
+        });
+        break;
+    case kRolloutRows:
+        rollout_gather_env_rows_kernel<<<plan.grid_x, plan.block, 0, stream>>>(
+            series, T, N, F, W, first, updates, weights, carry, T_rec, B, ring_mode, t_idx, env, S, s,
+            make_fastdiv((uint32_t)F));
+        break;
+    default: return PMENV_ERR_ARG;
+    }
+    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
+const char* pmenv_rollout_gather_env_path(int32_t N, int32_t F, int32_t W, int32_t S, int32_t aligned) {
+    thread_local char text[160];
+    text[0] = 0;
+    if (N < 1 || F < 2 || W < 1 || S < 1 || aligned < 0 || aligned > 3) return text;
+    replay_plan_describe(PMENV_REPLAY_ROLLOUT, replay_plan_rollout(N, F, W, S, aligned), text, sizeof(text), true);
+    return text;
+}
+
 int pmenv_metrics(const double* returns, const double* values, const float* weights, int32_t T, int32_t B, int32_t N,
                   double risk_free_rate, double periods, double* out, hipStream_t stream) {
     if (!returns || !values || !weights || !out || T < 1 || B < 1 || N < 1 || !(periods > 0.0)) return PMENV_ERR_ARG;

@@ -70,24 +70,54 @@ static __global__ void replay_gather_kernel(const float* series, int T, int N, i
 
 constexpr int kRowGatherUnroll = 8;   // rows of W*F <= 512 floats: all loads first
 
+// The per-env form of the map (pmenv_rollout_gather_env: envs that restart on their own, and
+// rollouts that resume): the window (t, b) starts at day first[t, b] and has seen
+// u = updates[t, b] ring updates since its env's last reset, so its history row is
+// r = u + c, rows < W-1 zero and row W-1 = e0 as above, and a row r > W-1 is the w' of step
+// t + c - W + 1 of this rollout: weights row carry + t + c - W ([carry + T_rec, B, N], the
+// first `carry` rows the steps before the rollout began). Lockstep is first = start + t,
+// u = t, carry = 0. What one sample's window depends on:
+struct RolloutWin {
+    int d0;         // series day of the window's first day
+    int u;          // ring updates since the env's last reset
+    int shift;      // weights row of history row r: r - W + shift (carry + t - u; lockstep 0)
+    int rows;       // weights rows there are (the per-env form's upper guard)
+    bool storage;   // the ring is full and read in storage order
+};
+__device__ __forceinline__ RolloutWin rollout_win_lockstep(const int32_t* start, int W, int ring_mode, int b, int t) {
+    return RolloutWin{start[b] + t, t, 0, 0, ring_mode == PMENV_RING_STORAGE && t >= W - 1};
+}
+__device__ __forceinline__ RolloutWin rollout_win_env(const int32_t* first, const int32_t* updates, int carry,
+                                                      int T_rec, int W, int B, int ring_mode, int b, int t) {
+    const size_t at = (size_t)t * B + b;
+    const int u = updates[at];
+    return RolloutWin{first[at], u, carry + t - u, carry + T_rec, ring_mode == PMENV_RING_STORAGE && u >= W - 1};
+}
+// the weight channel at window position p. ENV: a row outside the recorded history reads 0
+// (the lockstep rows are in range by r > W-1)
+template <bool ENV>
+__device__ __forceinline__ float rollout_weight(const RolloutWin& w, const float* weights, int W, int B, int N,
+                                                int b, int n, int p) {
+    const int c = w.storage ? (((p - w.u - 1) % W) + W) % W : p;
+    const int r = w.u + c;                         // history row
+    if (r < W - 1) return 0.0f;
+    if (r == W - 1) return n == 0 ? 1.0f : 0.0f;
+    if (!ENV) return weights[((size_t)(r - W) * B + b) * N + n];
+    const int row = r - W + w.shift;
+    if (row < 0 || row >= w.rows) return 0.0f;
+    return weights[((size_t)row * B + b) * N + n];
+}
+
 // The map above, one wave per (sample, asset) row of W*F floats: a lane writes floats
 // lane, lane + 64, ... of the row (each store one contiguous 256-B run), the day and
 // channel from the row offset by one multiply-shift, the sample's env / step / start
 // wave-uniform. The float-per-thread form (tools build) spends its time in 64-bit divisions.
-static __global__ __launch_bounds__(256) void rollout_gather_rows_kernel(const float* series, int T, int N, int F, int W,
-                                                                  const int32_t* start, const float* weights,
-                                                                  int B, int ring_mode, const int32_t* t_idx,
-                                                                  const int32_t* env, int S, float* s, FastDiv div_f) {
-    const int64_t rowi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (rowi >= (int64_t)S * N) return;
-    const int lane = threadIdx.x & 63;
-    const int j = __builtin_amdgcn_readfirstlane((int)(rowi / N));
-    const int n = __builtin_amdgcn_readfirstlane((int)(rowi - (int64_t)j * N));
-    const int b = env[j], t = t_idx[j];
-    const int d0 = start[b] + t;
+template <bool ENV>
+__device__ __forceinline__ void rollout_gather_rows_body(const float* series, int T, int N, int F, int W,
+                                                         const RolloutWin& win, const float* weights, int B, int b,
+                                                         int n, int lane, float* out, FastDiv div_f) {
+    const int d0 = win.d0;
     const int Fm = F - 1, WF = W * F;
-    const bool storage = ring_mode == PMENV_RING_STORAGE && t >= W - 1;
-    float* out = s + rowi * WF;
     // the value of row float i: a series or a weight-history float, or a constant
     auto fetch = [&](int i) -> float {
         const int p = (int)fdiv((uint32_t)i, div_f), f = i - p * F;
@@ -95,11 +125,7 @@ static __global__ __launch_bounds__(256) void rollout_gather_rows_kernel(const f
             const int d = d0 + p;
             return (d >= 0 && d < T) ? series[((size_t)d * N + n) * Fm + f] : NAN;
         }
-        const int c = storage ? (((p - t - 1) % W) + W) % W : p;
-        const int r = t + c;                       // history row
-        if (r < W - 1) return 0.0f;
-        if (r == W - 1) return n == 0 ? 1.0f : 0.0f;
-        return weights[((size_t)(r - W) * B + b) * N + n];
+        return rollout_weight<ENV>(win, weights, W, B, N, b, n, p);
     };
     if (WF <= 64 * kRowGatherUnroll) {             // every load of the row in flight before the stores
         float v[kRowGatherUnroll];
@@ -113,6 +139,35 @@ static __global__ __launch_bounds__(256) void rollout_gather_rows_kernel(const f
     for (int i = lane; i < WF; i += 64) out[i] = fetch(i);
 }
 
+static __global__ __launch_bounds__(256) void rollout_gather_rows_kernel(const float* series, int T, int N, int F, int W,
+                                                                  const int32_t* start, const float* weights,
+                                                                  int B, int ring_mode, const int32_t* t_idx,
+                                                                  const int32_t* env, int S, float* s, FastDiv div_f) {
+    const int64_t rowi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (rowi >= (int64_t)S * N) return;
+    const int lane = threadIdx.x & 63;
+    const int j = __builtin_amdgcn_readfirstlane((int)(rowi / N));
+    const int n = __builtin_amdgcn_readfirstlane((int)(rowi - (int64_t)j * N));
+    const int b = env[j], t = t_idx[j];
+    rollout_gather_rows_body<false>(series, T, N, F, W, rollout_win_lockstep(start, W, ring_mode, b, t), weights, B,
+                                    b, n, lane, s + rowi * (W * F), div_f);
+}
+// the per-env form: first / updates [T_rec + 1, B] in place of start, weights [carry + T_rec, B, N]
+static __global__ __launch_bounds__(256) void rollout_gather_env_rows_kernel(
+    const float* series, int T, int N, int F, int W, const int32_t* first, const int32_t* updates,
+    const float* weights, int carry, int T_rec, int B, int ring_mode, const int32_t* t_idx, const int32_t* env, int S,
+    float* s, FastDiv div_f) {
+    const int64_t rowi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (rowi >= (int64_t)S * N) return;
+    const int lane = threadIdx.x & 63;
+    const int j = __builtin_amdgcn_readfirstlane((int)(rowi / N));
+    const int n = __builtin_amdgcn_readfirstlane((int)(rowi - (int64_t)j * N));
+    const int b = env[j], t = t_idx[j];
+    rollout_gather_rows_body<true>(series, T, N, F, W,
+                                   rollout_win_env(first, updates, carry, T_rec, W, B, ring_mode, b, t), weights, B, b,
+                                   n, lane, s + rowi * (W * F), div_f);
+}
+
 // One workgroup per sample (F = 5, the sample's [W, N] weight block and [W, N, 4] market
 // block fit LDS): both blocks are staged with coalesced reads — the market block is W
 // consecutive series days, contiguous in [T, N, 4]; each history row's N weights are one
@@ -121,21 +176,17 @@ static __global__ __launch_bounds__(256) void rollout_gather_rows_kernel(const f
 // line is fetched once per sample, where the per-row form fetches it per asset row.
 // NT: cache-policy bits of the window stores (0: plain stores; the product: 16, sc1, for
 // windows <= 128 MiB, else 2, nt; the tools build A/Bs the others)
-template <int NT = 0>
-__global__ __launch_bounds__(256) void rollout_gather_tile_kernel(const float* series, int T, int N, int W,
-                                                                  const int32_t* start, const float* weights, int B,
-                                                                  int ring_mode, const int32_t* t_idx,
-                                                                  const int32_t* env, float* s, FastDiv div_n,
-                                                                  FastDiv div_wf, FastDiv div_f) {
+template <int NT, bool ENV>
+__device__ __forceinline__ void rollout_gather_tile_body(const float* series, int T, int N, int W,
+                                                         const RolloutWin& win, const float* weights, int B, int b,
+                                                         int j, float* s, FastDiv div_n, FastDiv div_wf,
+                                                         FastDiv div_f) {
     constexpr int F = 5;
     extern __shared__ __attribute__((aligned(16))) float sh[];   // market [W][N][4], then weights [W][N]
     float* sh_m = sh;
     float* sh_w = sh + (size_t)W * N * 4;
     const int tid = threadIdx.x;
-    const int j = blockIdx.x;
-    const int b = env[j], t = t_idx[j];
-    const int d0 = start[b] + t;
-    const bool storage = ring_mode == PMENV_RING_STORAGE && t >= W - 1;
+    const int d0 = win.d0;
     const int nd = W * N;                          // market: one f4 per (day, asset); weights: one float
     const f4* src = reinterpret_cast<const f4*>(series) + (size_t)d0 * N;
     f4* sh_m4 = reinterpret_cast<f4*>(sh_m);
@@ -152,10 +203,7 @@ __global__ __launch_bounds__(256) void rollout_gather_tile_kernel(const float* s
                 const int p = (int)fdiv((uint32_t)i, div_n), n = i - p * N;
                 const int d = d0 + p;
                 if (d >= 0 && d < T) m[k] = src[i];        // days outside the series read NaN
-                const int c = storage ? (((p - t - 1) % W) + W) % W : p;
-                const int r = t + c;                       // history row
-                if (r == W - 1) w[k] = n == 0 ? 1.0f : 0.0f;
-                else if (r > W - 1) w[k] = weights[((size_t)(r - W) * B + b) * N + n];
+                w[k] = rollout_weight<ENV>(win, weights, W, B, N, b, n, p);
             }
         }
 #pragma unroll
@@ -192,6 +240,30 @@ __global__ __launch_bounds__(256) void rollout_gather_tile_kernel(const float* s
         if constexpr (NT == 0) out[q] = f4{v[0], v[1], v[2], v[3]};
         else buf_store4<NT>(make_rsrc(out, (uint32_t)nq * 16u), (uint32_t)q * 16u, f4{v[0], v[1], v[2], v[3]});
     }
+}
+
+template <int NT = 0>
+__global__ __launch_bounds__(256) void rollout_gather_tile_kernel(const float* series, int T, int N, int W,
+                                                                  const int32_t* start, const float* weights, int B,
+                                                                  int ring_mode, const int32_t* t_idx,
+                                                                  const int32_t* env, float* s, FastDiv div_n,
+                                                                  FastDiv div_wf, FastDiv div_f) {
+    const int j = blockIdx.x;
+    const int b = env[j], t = t_idx[j];
+    rollout_gather_tile_body<NT, false>(series, T, N, W, rollout_win_lockstep(start, W, ring_mode, b, t), weights, B,
+                                        b, j, s, div_n, div_wf, div_f);
+}
+// the per-env form, as rollout_gather_env_rows_kernel
+template <int NT = 0>
+__global__ __launch_bounds__(256) void rollout_gather_env_tile_kernel(
+    const float* series, int T, int N, int W, const int32_t* first, const int32_t* updates, const float* weights,
+    int carry, int T_rec, int B, int ring_mode, const int32_t* t_idx, const int32_t* env, float* s, FastDiv div_n,
+    FastDiv div_wf, FastDiv div_f) {
+    const int j = blockIdx.x;
+    const int b = env[j], t = t_idx[j];
+    rollout_gather_tile_body<NT, true>(series, T, N, W,
+                                       rollout_win_env(first, updates, carry, T_rec, W, B, ring_mode, b, t), weights,
+                                       B, b, j, s, div_n, div_wf, div_f);
 }
 
 

@@ -192,7 +192,7 @@ inline ReplayPlan replay_plan_seq(int N, int F, int W, int L, int S, int aligned
     return p;
 }
 
-// pmenv_rollout_gather
+// pmenv_rollout_gather and pmenv_rollout_gather_env
 inline ReplayPlan replay_plan_rollout(int N, int F, int W, int S, int aligned) {
     ReplayPlan p;
     const int64_t lds = (int64_t)W * N * F * (int64_t)sizeof(float);
@@ -235,8 +235,9 @@ inline ReplayPlan replay_plan(int kind, int N, int F, int W, int n, int S, int a
 }
 
 // pmenv_replay_path's string for a plan: the kernel as the library instantiates it, then
-// R, the staged days and the sequence chunks where the form has them, the grid and the LDS bytes
-inline void replay_plan_describe(int kind, const ReplayPlan& p, char* out, size_t size) {
+// R, the staged days and the sequence chunks where the form has them, the grid and the LDS bytes.
+// env: the rollout forms' per-env kernels (pmenv_rollout_gather_env: the same plan)
+inline void replay_plan_describe(int kind, const ReplayPlan& p, char* out, size_t size, bool env = false) {
     static const char* const stem[] = {"replay_gather", "replay_nstep", "replay_seq"};
     char name[64] = "";
     if (size) out[0] = 0;
@@ -244,8 +245,10 @@ inline void replay_plan_describe(int kind, const ReplayPlan& p, char* out, size_
     case kReplayF5p: snprintf(name, sizeof(name), "%s_f5p_kernel<%d,%d>", stem[kind], p.ppt, p.policy); break;
     case kReplayLds: snprintf(name, sizeof(name), "%s_lds_kernel", stem[kind]); break;
     case kReplayElem: snprintf(name, sizeof(name), "%s_kernel", stem[kind]); break;
-    case kRolloutTile: snprintf(name, sizeof(name), "rollout_gather_tile_kernel<%d>", p.policy); break;
-    case kRolloutRows: snprintf(name, sizeof(name), "rollout_gather_rows_kernel"); break;
+    case kRolloutTile:
+        snprintf(name, sizeof(name), "rollout_gather_%stile_kernel<%d>", env ? "env_" : "", p.policy);
+        break;
+    case kRolloutRows: snprintf(name, sizeof(name), "rollout_gather_%srows_kernel", env ? "env_" : ""); break;
     default: return;
     }
     int at = snprintf(out, size, "%s R=%d", name, p.R);

@@ -19,7 +19,8 @@ PMENV_ABI_VERSION = 4   # 2: pmenv_window_written / pmenv_state_written; cfg def
                         #    (pmenv_replay_gather_seq, pmenv_prio_*, pmenv_restart_days and
                         #    pmenv_replay_path added under 4: load() names a missing symbol;
                         #    pmenv_replay_valid_build / _select, pmenv_replay_gather_nstep_env /
-                        #    _seq_env and pmenv_prio_fill_env likewise)
+                        #    _seq_env and pmenv_prio_fill_env likewise; pmenv_rollout_gather_env and
+                        #    pmenv_rollout_gather_env_path likewise)
 
 # enums (include/pmenv.h)
 REWARD_KINDS = {"log_returns": 0, "returns": 1, "sharpe_ratio": 2, "diff_sharpe": 3}
@@ -122,6 +123,9 @@ SIGNATURES = [
     ("pmenv_prio_update", ctypes.c_int, [_P, _I64, _P, _P, _I32, _F, _F, _P]),
     ("pmenv_rollout_gather", ctypes.c_int,
      [_P, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _P, _P]),
+    ("pmenv_rollout_gather_env", ctypes.c_int,
+     [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _P]),
+    ("pmenv_rollout_gather_env_path", ctypes.c_char_p, [_I32, _I32, _I32, _I32, _I32]),
     ("pmenv_metrics", ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, ctypes.c_double, ctypes.c_double, _P, _P]),
     ("pmenv_batch_reward_workspace", _SZ, [_I32]),
     ("pmenv_batch_reward_forward", ctypes.c_int,

@@ -50,7 +50,7 @@ class WindowCritic(torch.nn.Module):
 
 class OnPolicy:
     def __init__(self, env, policy, horizon, series=None, lr=1e-3, batch_size=256, generator=None,
-                 explore_std=0.0, explore_seed=44, env_offset=0):
+                 explore_std=0.0, explore_seed=44, env_offset=0, episodes=False):
         """series: a pmenv.MarketSeries — every env trades it from its own start day, in
         place, and the rollout buffer keeps actions, w', values and rewards only (compact,
         windows re-materialised at sample time); None: bars fed per step, the env advancing
@@ -59,12 +59,20 @@ class OnPolicy:
         centred N(0, I) draw keyed by (explore_seed, step, global env id, asset) — the
         stochastic policy update_actor_critic scores; env_offset is this rank's first global
         env id (pmenv.parallel.shard_range), so a sharded rollout draws exactly its slice of
-        the unsharded one's noise."""
+        the unsharded one's noise.
+        episodes=True (with series): the compact buffer's per-env form — rollout(episodes=ep)
+        lets every env end and restart its episode on its own (pmenv.episodes.Episodes) and
+        rollout(episodes=ep, resume=True) collects the next horizon from the envs as they
+        stand. The noise of the k-th consecutive resumed rollout is keyed by
+        explore_seed + (k << 32), so it differs from the rollouts before it; a rollout that
+        resets (resume=False) starts again at k = 0."""
         cfg = env.cfg
         self.env, self.policy = env, policy
         self.buf = DeviceRolloutBuffer(cfg.num_envs, cfg.num_assets, cfg.window, horizon, cfg.features,
                                        device=env.device, init_cash=cfg.init_cash, close_channel=cfg.close_channel,
-                                       series=series, ring=cfg.ring)
+                                       series=series, ring=cfg.ring, episodes=episodes)
+        self.obs = None
+        self._resumed = 0              # consecutive resumed rollouts (keys the exploration noise)
         self.optim = torch.optim.Adam(policy.parameters(), lr=lr)
         self.batch_size = batch_size
         self.generator = generator
@@ -92,21 +100,52 @@ class OnPolicy:
         N(0, 1) logits keyed by step, global env id and asset) minus its mean over assets."""
         from . import synth
         buf = self.buf
-        la = torch.log(synth.actions(buf.T, buf.B, buf.N, env_offset=self.env_offset, seed=self.explore_seed,
-                                     device=self.env.device))
+        la = torch.log(synth.actions(buf.T, buf.B, buf.N, env_offset=self.env_offset,
+                                     seed=self.explore_seed + (self._resumed << 32), device=self.env.device))
         self._noise = la - la.mean(dim=-1, keepdim=True)
         self._u = torch.empty_like(self._noise)          # [T, B, N] sampled centred logits (act)
 
-    def rollout(self, obs0=None, bars=None, start=None):
+    def rollout(self, obs0=None, bars=None, start=None, episodes=None, resume=False):
         """train/on_policy.py:59-67 for every env at once. Slab form: obs0 [B, N, W, F] is
         the reset window and bars[t] the day's [B, N, F-1] bars (t = 0 .. horizon-1).
         Compact form (series given at construction): start [B] is every env's first day
         on the series; the window lives in the env (stepped in place) and only the
-        action, w', value and reward of each step are recorded."""
+        action, w', value and reward of each step are recorded.
+        Per-env episodes (OnPolicy(episodes=True)): episodes is the envs' pmenv.episodes.Episodes;
+        each step runs act -> env.step(day=episodes.next_day) -> record -> env.restart ->
+        record done / first. resume=False resets the envs on episodes.start's windows (a fresh
+        Episodes); resume=True keeps the envs, their windows and `episodes` where the last
+        rollout left them. The recorded dones are in buf.done[1:]."""
         buf, env = self.buf, self.env
         rewards = []
+        if episodes is not None:
+            if not buf.episodes:
+                raise ValueError("rollout(episodes=) needs OnPolicy(series=..., episodes=True)")
+            if resume and self.obs is None:
+                raise ValueError("resume=True continues a rollout: run one with resume=False first")
+            self._resumed = self._resumed + 1 if resume else 0
+        elif resume or buf.episodes:
+            raise ValueError("an episodes buffer rolls out with rollout(episodes=...); resume needs it too")
         if self.explore_std > 0.0:
             self._draw_noise()
+        if episodes is not None:
+            series, ep = buf.series, episodes
+            if resume:
+                buf.resume()
+                obs = self.obs
+            else:
+                buf.reset(start=ep.start)
+                obs = series.initial_window(ep.start, buf.W)
+                env.reset(obs)
+            w = torch.empty(buf.B, buf.N, device=env.device)
+            for t in range(1, buf.T + 1):
+                a = self.act(obs, t)
+                r, _ = env.step(a, obs, series=series, day=ep.next_day, weights_out=w)
+                buf.add(a, env.value, r, weights=w)          # the value before the restart overwrites it
+                buf.restarted(env.restart(obs, ep), ep.next_day)
+                rewards.append(r)
+            self.obs = obs
+            return torch.stack(rewards)
         if buf.compact:
             series = buf.series
             start = torch.as_tensor(start, device=env.device).to(torch.int32).reshape(buf.B)

@@ -62,7 +62,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default="")
-    ap.add_argument("--only", default="", help="comma list of f1,f2,f3,f4,prio (default: all)")
+    ap.add_argument("--only", default="", help="comma list of f1,f2,f3,f4,prio,rollout_env (default: all; rollout_env is part of f1)")
+    ap.add_argument("--parent-lib", default="", help="rollout_env: another build's libpmenv.so (the parent commit's), "
+                    "whose pmenv_rollout_gather is timed beside this build's in the same process")
     a = ap.parse_args()
     only = set(a.only.split(",")) if a.only else {"f1", "f2", "f3", "f4", "prio"}
     dev = torch.device("cuda:0")
@@ -158,6 +160,70 @@ def main():
             work = torch.empty(lib.pmenv_moments_workspace() // 8, dtype=torch.float64, device=dev)
             us = timeit(lambda: ck(lib.pmenv_moments(P(x), n, P(out), P(work), st), "moments"), a.reps)
             res.append(row("moments", us, n * 4, n=n))
+
+    if "f1" in only or "rollout_env" in only:
+        # the compact rollout's per-env form (pmenv_rollout_gather_env) beside the lockstep gather
+        # at config 2's buffer (4,096 envs x 32 steps, S = 4,096, N 30, W 50), same process, same
+        # samples, alternating: fed the lockstep bookkeeping (first = start + t, updates = t; the
+        # same bits), then envs that restart every 8-40 steps, each from its own phase. carry = W
+        # with zero carry rows, as DeviceRolloutBuffer(episodes=True) holds them
+        Bc, Tr, S, N_, W_ = 4096, 32, 4096, 30, 50
+        Ts = Tr + W_ + 48
+        ser_c = torch.rand(Ts, N_, 4, device=dev, generator=g)
+        start = torch.randint(0, 8, (Bc,), device=dev, generator=g).to(torch.int32)
+        wts = torch.rand(Tr, Bc, N_, device=dev, generator=g)
+        wts_c = torch.cat([torch.zeros(W_, Bc, N_, device=dev), wts]).contiguous()
+        tix = torch.randint(0, Tr + 1, (S,), device=dev, generator=g).to(torch.int32)
+        eix = torch.randint(0, Bc, (S,), device=dev, generator=g).to(torch.int32)
+        out_l, out_e = torch.empty(S, N_, W_, 5, device=dev), torch.empty(S, N_, W_, 5, device=dev)
+        trow = torch.arange(Tr + 1, device=dev, dtype=torch.int32)[:, None]
+        first_l = (start[None, :] + trow).contiguous()
+        upd_l = trow.repeat(1, Bc).contiguous()
+        length = torch.randint(8, 41, (Bc,), device=dev, generator=g).to(torch.int32)
+        phase = (torch.rand(Bc, device=dev, generator=g) * length).to(torch.int32)
+        upd_r = ((trow + phase[None, :]) % length[None, :]).contiguous()       # <= 39 < t + carry
+        first_r = (start[None, :] + upd_r).contiguous()
+
+        def lock(lib=lib):
+            ck(lib.pmenv_rollout_gather(P(ser_c), Ts, N_, 5, W_, P(start), P(wts), Tr, Bc, 0, P(tix), P(eix), S,
+                                        P(out_l), st), "rollout_gather")
+
+        def env_form(first, upd):
+            ck(lib.pmenv_rollout_gather_env(P(ser_c), Ts, N_, 5, W_, P(first), P(upd), P(wts_c), W_, Tr, Bc, 0,
+                                            P(tix), P(eix), S, P(out_e), st), "rollout_gather_env")
+        lock()
+        env_form(first_l, upd_l)
+        same = bool(torch.equal(out_l.view(torch.int32), out_e.view(torch.int32)))
+        old = None
+        if a.parent_lib:                       # the parent build's lockstep gather, same process
+            old = ctypes.CDLL(a.parent_lib)
+            old.pmenv_rollout_gather.restype, old.pmenv_rollout_gather.argtypes = next(
+                (r, t) for n, r, t in _abi.SIGNATURES if n == "pmenv_rollout_gather")
+            out_new = out_l.clone()
+            out_l.zero_()
+            lock(old)
+            same_old = bool(torch.equal(out_l.view(torch.int32), out_new.view(torch.int32)))
+        tl, te, tr_, tp = [], [], [], []
+        for _ in range(5):
+            tl.append(timeit(lock, a.reps))
+            if old is not None:
+                tp.append(timeit(lambda: lock(old), a.reps))
+            te.append(timeit(lambda: env_form(first_l, upd_l), a.reps))
+            tr_.append(timeit(lambda: env_form(first_r, upd_r), a.reps))
+        base, us_e, us_r = statistics.median(tl), statistics.median(te), statistics.median(tr_)
+        alg = S * N_ * W_ * 5 * 4
+        kw = dict(B=Bc, T=Tr, S=S, N=N_, W=W_)
+        res.append(row("rollout_gather_lockstep", base, alg, spread=round((max(tl) - min(tl)) / base, 4), **kw))
+        if old is not None:
+            us_p = statistics.median(tp)
+            res.append(row("rollout_gather_lockstep_parent", us_p, alg, ratio_this_to_parent=round(base / us_p, 4),
+                           spread=round((max(tp) - min(tp)) / us_p, 4), same_bits=same_old, **kw))
+        res.append(row("rollout_gather_env", us_e, alg, ratio=round(us_e / base, 4),
+                       spread=round((max(te) - min(te)) / us_e, 4), same_bits=same, **kw))
+        res.append(row("rollout_gather_env_restarts", us_r, alg, ratio=round(us_r / base, 4),
+                       spread=round((max(tr_) - min(tr_)) / us_r, 4),
+                       restarts_per_env=round(float((upd_r[1:] == 0).float().sum(0).mean()), 2), **kw))
+        del ser_c, wts, wts_c, out_l, out_e
 
     if "f2" in only:
         # differentiable batched PG reward: forward (reward only; the product's two launches
