@@ -44,7 +44,8 @@ extern "C" {
  *    kernel by name, likewise; pmenv_replay_valid_build, pmenv_replay_valid_select,
  *    pmenv_replay_gather_nstep_env, pmenv_replay_gather_seq_env and pmenv_prio_fill_env, the
  *    replay of envs that end their episodes on their own, likewise; pmenv_rollout_gather_env and
- *    pmenv_rollout_gather_env_path, the compact rollout of such envs, likewise) */
+ *    pmenv_rollout_gather_env_path, the compact rollout of such envs, likewise;
+ *    pmenv_metrics_episodes, the trajectory metrics of such envs per episode, likewise) */
 #define PMENV_ABI_VERSION 4
 
 /* Opaque HIP stream (identical to HIP's own typedef); NULL = default stream. */
@@ -666,6 +667,51 @@ const char* pmenv_rollout_gather_env_path(int32_t N, int32_t F, int32_t W, int32
  * quantstats is absent). */
 int pmenv_metrics(const double* returns, const double* values, const float* weights, int32_t T, int32_t B,
                   int32_t N, double risk_free_rate, double periods, double* out, hipStream_t stream);
+
+/* The same five metrics per episode, for envs that end their episodes on their own
+ * (pmenv_restart_days): the reference's Metrics are per episode ("walk the series to its end",
+ * then metrics.write(), train/off_policy.py:96-110).
+ *
+ * A record of T consecutive steps of B envs; steps are t = 1 .. T:
+ *   returns    [T, B] f64      row t-1 is step t's simple return;
+ *   values     [T+1, B] f64    row 0 is the value before step 1, row t the value after step t;
+ *                              where step t ended an episode this is the terminal value, copied
+ *                              before the restart overwrote it (as DeviceRolloutBuffer.add does);
+ *   weights    [T+1, B, N] f32 post-drift weights, same rows as values;
+ *   dones      [T, B] uint8    row t-1 nonzero (any nonzero byte) means step t ended env b's
+ *                              episode: the layout pmenv_gae and episodes.collect use;
+ *   init_value f64             the value every restarted env begins from.
+ * The weights a restarted env begins from are e0 (1 for asset 0, else 0).
+ *
+ * Segments of env b. Let d_1 < .. < d_m be the steps with a nonzero done and e_0 = 0. Segment
+ * k (0-based) covers steps first = e_k + 1 .. last = e_{k+1}, with e_{k+1} = d_{k+1}; if
+ * d_m < T, or m = 0, one last open segment ends at T. count[b] is the number of segments,
+ * always >= 1; n = last - first + 1.
+ *
+ * Per segment, pmenv_metrics' definitions applied to the segment:
+ *   x_t = returns[t-1, b] - rfp for t in the segment, rfp = (1 + rf)^(1/periods) - 1, or 0
+ *   when rf = 0;
+ *   sharpe  = mean(x) / std(x, ddof = 1) * sqrt(periods);
+ *   sortino = mean(x) / sqrt(sum min(x, 0)^2 / n) * sqrt(periods);
+ *   value path P = [V0, values[first .. last, b]], V0 = values[0, b] for k = 0, else init_value;
+ *   max drawdown = min(0, min_i (P_i / max_{j <= i} P_j - 1));
+ *   average turnover = sum_{t = first .. last} sum_n |weights[t, b, n] - prev| / n, prev =
+ *   weights[t-1, b, n], except at t = first of a segment with k > 0, where prev is e0;
+ *   final value = values[last, b]: a copy, bit-equal.
+ *
+ * Outputs, padded to the caller's cap K = max_episodes (no allocation, no prefix sum over
+ * envs, no host read): out [B, K, 5] f64 in pmenv_metrics' field order, span [B, K, 2] int32 =
+ * {first, last}, count [B] int32. Segments k < min(count[b], K) are stored in chronological
+ * order; slots count[b] <= k < K get NaN in out and {0, 0} in span; count[b] is exact even when
+ * it exceeds K (the first K segments are kept). A stored segment is closed iff
+ * dones[last - 1, b] != 0. No atomics: the same bits on every call and for every K.
+ *
+ * Enqueues one launch on `stream`; never allocates, frees or synchronises (capturable).
+ * PMENV_ERR_ARG: a NULL pointer, max_episodes < 1, or pmenv_metrics' shape errors. */
+int pmenv_metrics_episodes(const double* returns, const double* values, const float* weights,
+                           const uint8_t* dones, int32_t T, int32_t B, int32_t N, double init_value,
+                           double risk_free_rate, double periods, int32_t max_episodes, double* out,
+                           int32_t* span, int32_t* count, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -3,9 +3,9 @@
 // step_flat.h (the one-launch step over fixed window tiles), step_env.h (the one-launch
 // step, one workgroup per env), env_step.h (scalar step, window streams, reset,
 // fallbacks), scalar_vec.h (packed scalar step), data.h (synthetic market data),
-// rollout.h (GAE, moments), replay.h (replay gather, metrics) and trainer.h (batched
-// reward); the step's launchers in launch.h, the handle and its shape planning in handle.h,
-// the sample gathers' kernel choice in replay_plan.h.
+// rollout.h (GAE, moments), replay.h (replay gather, metrics), metrics_env.h (the metrics
+// per episode) and trainer.h (batched reward); the step's launchers in launch.h, the
+// handle and its shape planning in handle.h, the sample gathers' kernel choice in replay_plan.h.
 //
 // Every entry point enqueues on the caller's stream and never synchronises, allocates or
 // frees (graph-capturable), except create / destroy / the explicit synchronous queries
@@ -29,6 +29,7 @@
 #include "episode.h"
 #include "handle.h"
 #include "launch.h"
+#include "metrics_env.h"
 #include "prio.h"
 #include "replay.h"
 #include "replay_valid.h"
@@ -1758,6 +1759,22 @@ int pmenv_metrics(const double* returns, const double* values, const float* weig
     metrics_fused_kernel<<<(unsigned)(nseg + nturn), 256, 0, stream>>>(returns, values, weights, T, B, N,
                                                                        risk_free_rate, periods, tpe, eb, nseg,
                                                                        nturn, 1, out);
+    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
+int pmenv_metrics_episodes(const double* returns, const double* values, const float* weights, const uint8_t* dones,
+                           int32_t T, int32_t B, int32_t N, double init_value, double risk_free_rate, double periods,
+                           int32_t max_episodes, double* out, int32_t* span, int32_t* count, hipStream_t stream) {
+    if (!returns || !values || !weights || !dones || !out || !span || !count || T < 1 || B < 1 || N < 1 ||
+        !(periods > 0.0) || max_episodes < 1)
+        return PMENV_ERR_ARG;
+    // pmenv_metrics' geometry: a segment-walk block per 64 envs, then the turnover blocks
+    // (N <= 64: whole envs per wave, so eb is four times a wave's envs)
+    const int tpe = N <= 256 ? N : 256, eb = N <= 64 ? 4 * (64 / N) : 256 / tpe;
+    const int nseg = (B + 63) / 64, nturn = (B + eb - 1) / eb;
+    metrics_env_fused_kernel<<<(unsigned)(nseg + nturn), 256, 0, stream>>>(
+        returns, values, weights, dones, T, B, N, init_value, risk_free_rate, periods, max_episodes, tpe, eb, nseg,
+        out, span, count);
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
 

@@ -127,6 +127,8 @@ SIGNATURES = [
      [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _P]),
     ("pmenv_rollout_gather_env_path", ctypes.c_char_p, [_I32, _I32, _I32, _I32, _I32]),
     ("pmenv_metrics", ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, ctypes.c_double, ctypes.c_double, _P, _P]),
+    ("pmenv_metrics_episodes", ctypes.c_int,
+     [_P, _P, _P, _P, _I32, _I32, _I32, ctypes.c_double, ctypes.c_double, ctypes.c_double, _I32, _P, _P, _P, _P]),
     ("pmenv_batch_reward_workspace", _SZ, [_I32]),
     ("pmenv_batch_reward_forward", ctypes.c_int,
      [_P, _P, _P, _I32, _I32, _I32, _I32, ctypes.c_double, _P, _P, _P, _P]),

@@ -26,6 +26,8 @@ first step's day is `day + 1 = start + window`.
 import numpy as np
 import torch
 
+from .config import RISK_FREE_RATE
+
 
 def _days_of(series):
     if hasattr(series, "days"):
@@ -153,3 +155,40 @@ def collect(env, series, episodes, obs, steps, act=None):
         rewards[t] = r
         dones[t] = env.restart(obs, episodes)
     return rewards, dones.bool()
+
+
+def evaluate(env, series, episodes, obs, steps, act=None, max_episodes=None, risk_free_rate=RISK_FREE_RATE,
+             periods=252):
+    """The `collect` loop as an evaluation run: per-episode Sharpe, Sortino, max drawdown,
+    average turnover and final value for envs that end their episodes on different steps
+    (the reference's Metrics are per episode: walk the series to its end, then metrics.write(),
+    train/off_policy.py:96-110). Per step it records the return (step(returns_out=) - 1), a
+    copy of env.value taken between step and restart — the terminal value where the step ended
+    an episode —, the step's post-drift weights and the done restart returns; row 0 holds the
+    envs' value and last post-drift weights at entry. Returns replay.episode_metrics(...) of
+    that record with init_value = env.cfg.init_cash; an env that is not freshly reset at entry
+    has its first episode measured from its entry value. max_episodes=None costs one host
+    read after the run."""
+    from .replay import episode_metrics
+    B, N = env.cfg.num_envs, env.cfg.num_assets
+    dev = env.device
+    rets = torch.empty(steps, B, dtype=torch.float64, device=dev)
+    vals = torch.empty(steps + 1, B, dtype=torch.float64, device=dev)
+    wts = torch.empty(steps + 1, B, N, dtype=torch.float32, device=dev)
+    dones = torch.empty(steps, B, dtype=torch.uint8, device=dev)
+    vals[0] = env.value
+    wts[0] = env.weights.get_last()
+    uniform = torch.full((B, N), 1.0 / N, device=dev) if act is None else None
+    for t in range(steps):
+        if uniform is not None:
+            a = uniform
+        elif callable(act):
+            with torch.no_grad():
+                a = act(obs)
+        else:
+            a = act[t]
+        env.step(a, obs, series=series, day=episodes.next_day, weights_out=wts[t + 1], returns_out=rets[t])
+        vals[t + 1] = env.value                   # before the restart puts init_cash back
+        dones[t] = env.restart(obs, episodes)
+    rets -= 1.0
+    return episode_metrics(rets, vals, wts, dones, env.cfg.init_cash, max_episodes, risk_free_rate, periods)

@@ -29,6 +29,7 @@ and `update` are the caller's callables.
 """
 import torch
 
+from . import episodes as _episodes
 from .replay import DeviceReplay, trajectory_metrics
 
 
@@ -179,3 +180,11 @@ class OffPolicy:
             return trajectory_metrics(rets, vals, wts)
         finally:
             env.track_info = track
+
+    def evaluate_episodes(self, ep, obs, steps, act=None, **kw):
+        """`evaluate` for envs that end their episodes on their own: pmenv.episodes.evaluate
+        over this loop's env and series — per-episode metrics, {name: [B, K]} with first /
+        last / count — with `act` (default: the loop's act; None: uniform weights). Records
+        nothing in the replay. kw: max_episodes, risk_free_rate, periods."""
+        return _episodes.evaluate(self.env, self.series, ep, obs, steps,
+                                  act if act is not None else self.act_fn, **kw)

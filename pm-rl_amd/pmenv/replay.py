@@ -597,3 +597,47 @@ def trajectory_metrics(returns, values, weights, risk_free_rate=RISK_FREE_RATE, 
                                  _p(out), st), None, "pmenv_metrics")
     keys = ("sharpe", "sortino", "max_drawdown", "average_turnover", "final_value")
     return {k: out[:, i] for i, k in enumerate(keys)}
+
+
+def episode_metrics(returns, values, weights, dones, init_value, max_episodes=None, risk_free_rate=RISK_FREE_RATE,
+                    periods=252):
+    """`trajectory_metrics` per episode, for envs that end their episodes on their own
+    (pmenv.episodes): returns [T, B], values [T+1, B], weights [T+1, B, N] as above — a row
+    that ended an episode holds the terminal value and weights, taken before the restart — and
+    dones [T, B] (bool / uint8, any nonzero byte: that step ended env b's episode). A restarted
+    env begins from `init_value` and the weights e0. Env b's record is cut into count[b] >= 1
+    episodes, the last one open unless the last row is a done (include/pmenv.h has the contract).
+    Returns {sharpe, sortino, max_drawdown, average_turnover, final_value: [B, K] f64, first,
+    last: [B, K] int32 (steps 1 .. T), count: [B] int32}; episodes k < min(count[b], K) in
+    chronological order, NaN / 0 in the slots past them; count is exact even above K.
+    max_episodes=None takes K = 1 + the most dones of any env, one host read; a caller who knows a bound
+    passes it and the call reads nothing back."""
+    lib = _abi.load()
+    r = returns.to(torch.float64).contiguous()
+    T, B = r.shape
+    v = values.to(device=r.device, dtype=torch.float64).contiguous()
+    w = weights.to(device=r.device, dtype=torch.float32).contiguous()
+    if tuple(v.shape) != (T + 1, B) or w.shape[:2] != (T + 1, B):
+        raise ValueError("values must be [T+1, B] and weights [T+1, B, N]")
+    if tuple(dones.shape) != (T, B):
+        raise ValueError("dones must be [T, B]")
+    d = dones.to(device=r.device)
+    if d.dtype != torch.uint8:                  # uint8 goes as it is: any nonzero byte is an episode end
+        d = d.ne(0).to(torch.uint8)
+    d = d.contiguous()
+    if max_episodes is None:
+        max_episodes = int(d.ne(0).sum(0).max()) + 1
+    K = int(max_episodes)
+    if K < 1:
+        raise ValueError("max_episodes must be at least 1")
+    out = torch.empty(B, K, 5, dtype=torch.float64, device=r.device)
+    span = torch.empty(B, K, 2, dtype=torch.int32, device=r.device)
+    count = torch.empty(B, dtype=torch.int32, device=r.device)
+    st = ctypes.c_void_p(torch.cuda.current_stream(r.device).cuda_stream)
+    _abi.check(lib.pmenv_metrics_episodes(_p(r), _p(v), _p(w), _p(d), T, B, w.shape[2], float(init_value),
+                                          float(risk_free_rate), float(periods), K, _p(out), _p(span), _p(count),
+                                          st), None, "pmenv_metrics_episodes")
+    keys = ("sharpe", "sortino", "max_drawdown", "average_turnover", "final_value")
+    res = {k: out[:, :, i] for i, k in enumerate(keys)}
+    res.update(first=span[:, :, 0], last=span[:, :, 1], count=count)
+    return res

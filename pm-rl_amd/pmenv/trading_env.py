@@ -434,7 +434,8 @@ class TradingEnv:
         episodes._restarted()
         return episodes.done
 
-    def step(self, action, features, prices=None, bar=None, out=None, series=None, day=None, weights_out=None):
+    def step(self, action, features, prices=None, bar=None, out=None, series=None, day=None, weights_out=None,
+             returns_out=None):
         """trading_env.py:44-105 for all B envs in one kernel launch.
 
         prices given, bar None : the reference contract — `features` is the next
@@ -452,6 +453,9 @@ class TradingEnv:
                                  window every day); returns (r, out).
         weights_out            : a float32 [B, N] GPU tensor that receives the
                                  post-drift weights w' (info["actions"], :83-85)
+        returns_out            : a float64 [B] GPU tensor that receives the step's
+                                 return ratio (info["returns"], :88-90), for callers
+                                 that keep their own record (restart forbids `info`)
         Returns (r, features); r is f32 [B] (0-dim for unbatched single-env input).
 
         Caller edits between fused in-place steps are honoured (the reference keeps no copy
@@ -464,7 +468,7 @@ class TradingEnv:
         if self._free:
             self._fit(features)
         if not features.is_cuda and bar is None and series is None and out is None and weights_out is None \
-                and prices is not None and self._HOST_DIRECT:
+                and returns_out is None and prices is not None and self._HOST_DIRECT:
             return self._step_host(action, features, prices)
         unb = self._obs_check(features)
         if not features.is_cuda:                    # the reference's CPU tensors: staged through the GPU
@@ -472,14 +476,15 @@ class TradingEnv:
                 raise ValueError("out must live where features does")
             dev_out = None if out is None else torch.empty(out.shape, dtype=out.dtype, device=self.device)
             r, res = self._step(action, features.to(self.device), prices, bar, dev_out, series, day,
-                                weights_out, unb, host=True)
+                                weights_out, unb, host=True, returns_out=returns_out)
             (features if out is None else out).copy_(res)
             self._host_io = True
             return r.cpu(), (features if out is None else out)
         if out is not None and not out.is_cuda:
             raise ValueError("out must live where features does")
         self._host_io = False
-        return self._step(action, features, prices, bar, out, series, day, weights_out, unb, host=False)
+        return self._step(action, features, prices, bar, out, series, day, weights_out, unb, host=False,
+                          returns_out=returns_out)
 
     # ------------------------------------------------------------------ host I/O
     # The reference driver's call shape (train/on_policy.py:59-67): CPU action, window and
@@ -570,7 +575,7 @@ class TradingEnv:
         val = self._rec_blk[2][i]
         self._hval, self._hval_ver = torch.from_numpy(val[0, ...] if unb else val), _version(self._state)
 
-    def _step(self, action, features, prices, bar, out, series, day, weights_out, unb, host):
+    def _step(self, action, features, prices, bar, out, series, day, weights_out, unb, host, returns_out=None):
         self._hval = None
         cfg = self.cfg
         B, N = cfg.num_envs, cfg.num_assets
@@ -619,10 +624,16 @@ class TradingEnv:
                     weights_out.device != self.device or weights_out.numel() != B * N:
                 raise ValueError(f"weights_out must be a contiguous float32 [{B}, {N}] tensor on {self.device}")
             args.weights = weights_out.data_ptr()
+        if returns_out is not None:
+            if returns_out.dtype != torch.float64 or not returns_out.is_contiguous() or \
+                    returns_out.device != self.device or returns_out.numel() != B:
+                raise ValueError(f"returns_out must be a contiguous float64 [{B}] tensor on {self.device}")
+            args.ret = returns_out.data_ptr()
         track = self.track_info and self._info is not None
-        if track:
+        if track and returns_out is None:
             ret = torch.empty(B, dtype=torch.float64, device=self.device)
             args.ret = ret.data_ptr()
+        if track:
             if weights_out is None:
                 w = torch.empty(B, N, dtype=torch.float32, device=self.device)
                 args.weights = w.data_ptr()
@@ -632,6 +643,8 @@ class TradingEnv:
         if track:
             # trading_env.py:80,85,90,100
             wv = w if weights_out is None else weights_out.reshape(B, N).clone()
+            if returns_out is not None:
+                ret = returns_out.reshape(B).clone()
             if host:
                 self._pending.append((self._value.clone(), wv, ret, r))
                 self._slot0_dirty = True
