@@ -45,7 +45,8 @@ extern "C" {
  *    pmenv_replay_gather_nstep_env, pmenv_replay_gather_seq_env and pmenv_prio_fill_env, the
  *    replay of envs that end their episodes on their own, likewise; pmenv_rollout_gather_env and
  *    pmenv_rollout_gather_env_path, the compact rollout of such envs, likewise;
- *    pmenv_metrics_episodes, the trajectory metrics of such envs per episode, likewise) */
+ *    pmenv_metrics_episodes, the trajectory metrics of such envs per episode, likewise;
+ *    pmenv_step_path_for, the step's kernels and geometry for a cfg without a device, likewise) */
 #define PMENV_ABI_VERSION 4
 
 /* Opaque HIP stream (identical to HIP's own typedef); NULL = default stream. */
@@ -257,8 +258,26 @@ int pmenv_reset_host(pmenv* h, float* obs, double* value, hipStream_t stream);
  * are not 16-B granular, "step_tiny_kernel" (one workgroup per env, the window staged in LDS:
  * env windows of at most 2,048 floats, N <= 64), "step_small_kernel" (one workgroup per env,
  * the window in registers: env windows of at most 16,384 floats) or "step_advance_lds_kernel" (the LDS-tiled
- * fallback, any F). */
+ * fallback, any F).
+ * The choice is the handle's shape plan: a pure function of its cfg and of
+ * pmenv_set_step_path, made by one host-only header (csrc/step_plan.h) that pmenv_create,
+ * pmenv_set_step_path, pmenv_step_ex's dispatch and this string all go through. */
 const char* pmenv_step_path(const pmenv* h);
+/* The same plan without a device or a handle: exactly what pmenv_step_path returns for a
+ * fresh handle of `cfg` after pmenv_set_step_path(path) (a pmenv_step_path_kind; the
+ * "device-sequenced" notes belong to a handle's history and never appear here). With
+ * detail != 0 the plan's geometry follows after " -- " as space-separated key=value fields
+ * in a fixed order, each printed whether or not the shape takes that form:
+ *   flat1=BxV (step_flat_kernel's threads x 16-B chunks per thread), relay=BxV:KL/KA
+ *   (step_relay_kernel's tiles and its scalar step's lanes per env / strided assets per lane),
+ *   stream_ip=BxV (the in-place flat stream), pol=DB/IP (the streams' cache policy, 1 = nt),
+ *   gen=BxV (advance_gen_kernel), k1= reg | lds | LxA | LxAs (the scalar step's form),
+ *   one_waves (step_env_kernel's waves per workgroup), small=BxE (step_small_kernel), tiny,
+ *   surf_stream (surface steps as scalar step + surface_stream_kernel), rows_per_tile and vec
+ *   (the LDS fallback).
+ * Returns "" for a cfg pmenv_create rejects, a path the shape does not fit, or NULL. The
+ * string lives in thread-local storage until the thread's next call. */
+const char* pmenv_step_path_for(const pmenv_cfg* cfg, int32_t path, int32_t detail);
 
 /* Advance-mode step implementation. AUTO (the default) picks per shape and window
  * mode; ONE_LAUNCH forces step_env_kernel (one workgroup per env: F = 5, W >= 2,

@@ -6,10 +6,10 @@
 #include <stdint.h>
 
 #include "../../include/pmenv.h"
+#include "step_plan.h"   // the host constants the kernels share with the plan (kBlock, kTileFloats, scratch_bytes, ...)
 
 namespace pmenv_dev {
 
-constexpr int kWideMaxAssets = 512;   // the widest env the packed scalar step and the wide flat step take
 // polls of a missing relay word before a tile defers (step_relay.h): each is an s_sleep plus an
 // agent-scope load round trip (~1 us under the stream), so ~1 ms — two orders of magnitude above
 // the scalar blocks' whole run, reached only when they were not dispatched ahead of the tile

@@ -21,13 +21,8 @@
 
 namespace pmenv_dev {
 
-constexpr int kBlock = 256;         // threads per env workgroup (LDS / surface / reset kernels)
-constexpr int kMaxVec = 8;          // float4 per thread for one LDS tile
-constexpr int kTileFloats = kBlock * kMaxVec * 4;  // 8192 floats = 32 KiB LDS tile
-constexpr int kScalarWaves = 4;     // envs (waves) per scalar_step_kernel workgroup
-constexpr int kStreamBlock = 512;   // threads per advance_rows_kernel workgroup
-
-// LDS carve of the per-env scalar scratch, behind an optional 16-B aligned tile region.
+// LDS carve of the per-env scalar scratch, behind an optional 16-B aligned tile region
+// (scratch_bytes in step_plan.h sizes it).
 struct Scratch {
     double* wv;   // [N] target weights, then portfolio values
     double* yv;   // [N] price relatives
@@ -49,10 +44,6 @@ __device__ __forceinline__ Scratch carve(float* lds, int tile_floats, int N, int
     s.wp_off = tile_floats + 4 * N + N;
     s.bar_off = s.wp_off + N;
     return s;
-}
-
-inline size_t scratch_bytes(int tile_floats, int N, int F) {
-    return (size_t)tile_floats * 4 + (size_t)N * 16 + (size_t)N * 8 + (size_t)N * (F - 1) * 4 + 16;
 }
 
 // ---------------------------------------------------------------- the scalar step

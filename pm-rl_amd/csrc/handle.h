@@ -1,5 +1,8 @@
-// handle.h — the env handle (struct pmenv) and the host-side shape planning, shared by the
-// product library (pmenv.hip, launch.h) and the tools build (tools/ab/pmenv_ab.hip).
+// handle.h — the env handle (struct pmenv) and the helpers of the host side that need HIP,
+// shared by the product library (pmenv.hip, launch.h) and the tools build
+// (tools/ab/pmenv_ab.hip). The handle is its shape plan (pmenv_host::StepPlan, step_plan.h:
+// every field that is a function of the cfg, host only) plus what the struct below declares:
+// the device memory, its streams and events, and the state that changes from step to step.
 //
 // The tools build — tools/libpmenv_ab.so, the A/B harnesses' library — is the product's
 // translation unit linked with tools/ab/pmenv_ab.hip, which defines the pmenv_tools hooks
@@ -16,8 +19,9 @@
 
 #include "../../include/pmenv.h"
 #include "common.h"
+#include "step_plan.h"
 
-struct pmenv {
+struct pmenv : pmenv_host::StepPlan {
     pmenv_cfg cfg;
     int device;
     void* state;          // value | stat_a | stat_b | counter | ring | nonfinite | last_close | w_new
@@ -31,55 +35,14 @@ struct pmenv {
     float* last_close;
     float* w_new;
     unsigned long long* nonfinite;
-    // the register step (step_small_kernel<small_block, small_e>): any F, any alignment, env
-    // windows of at most 1,024 x 16 floats; 0: the LDS fallback
-    int small_block, small_e;
-    bool tiny;            // ... of at most 256 x 8 floats and N <= 64: step_tiny_kernel (LDS-staged)
-    bool surf_stream;     // surface steps as two launches: the scalar step, then surface_stream_kernel
-    size_t surf_lds;      // its workgroup's rows' ring columns (rows x W floats)
-    // LDS single-launch fallback geometry
-    int rows_per_tile, tile_floats;
-    bool vec;
-    size_t lds_tile, lds_surface;
-    // two-launch path: the scalar step, then the window stream
-    bool streaming;       // F = 5, 16-B granular env windows: the streams below apply
-    int unit_rows, units_per_env, stream_vec;          // row-kernel advance in place
-    int unit_rows_db, units_per_env_db, stream_vec_db; // row-kernel advance double-buffered (obs_out)
-    bool flat_ok;         // the flat 16-B stream's shape rules hold
-    bool flat;            // double-buffered advance as the flat 16-B stream
-    int flat_pol, flat_ip_pol;   // cache policy (0 default, 1 nt): double-buffered / in-place stream
-    bool flat_inplace;    // in-place advance as the flat stream + halo (advance_flat_inplace_kernel)
-    int flat_ip_block, flat_ip_vec;   // threads per workgroup, chunks per thread
     float* halo;          // [halo_wgs][2] float4: first two chunks of every in-place flat workgroup
-    uint32_t halo_wgs, flat_qtot;
-    int scalar_scratch_floats;
-    size_t lds_scalar;
-    // two-launch path for F != 5 (2 <= F <= 8, 16-B granular env windows): the scalar step,
-    // then the generic stream (advance_gen_kernel<gen_block, gen_v>)
-    bool gen_ok;          // the shape fits the generic stream
-    int gen_auto;         // PMENV_FUSE_* bits the automatic choice gives it
-    int gen;              // PMENV_FUSE_* bits: which windows take it now
-    int gen_block, gen_v; // threads per workgroup, chunks per thread
-    uint32_t gen_qtot;    // chunks of the whole [B, N, W, F] window
-    int k1_vec;           // scalar_step_vec_kernel shape 100 * L + A (+ kK1Str), 0: register / LDS form
-    // one launch per step, one workgroup per env (step_env_kernel)
-    bool one_ok;          // the shape fits step_env_kernel
-    int one_auto;         // PMENV_FUSE_* bits the automatic choice gives step_env_kernel
-    int one;              // PMENV_FUSE_* bits: which windows take step_env_kernel now
-    int one_waves;        // waves per workgroup
-    uint32_t per4;        // 16-B chunks per env window
-    // one launch over the flat stream (step_flat_kernel / step_flat_vec_kernel)
-    bool flat1_ok;        // the shape fits the flat one-launch step
-    int flat1_auto;       // PMENV_FUSE_* bits the automatic choice gives it
-    int flat1;            // PMENV_FUSE_* bits: which windows take it now
-    int flat1_block, flat1_vec;   // threads per workgroup, chunks per thread
+    // the flat one-launch step's copies (step_flat_kernel / step_flat_vec_kernel)
     void* snap;           // the state snapshot, two parities: value f64 | counter i32 | get_last() | last close
     double* sv[2];
     int32_t* sk[2];
     float* sw[2];
     float* slc[2];
     float* halo1[2];      // [halo1_wgs][2] float4 per parity: the next tile's first two chunks
-    uint32_t halo1_wgs;
     int par;              // parity of the snapshot / halo the next step reads
     bool snap_ok;         // sv[par] .. slc[par] equal the canonical state
     const float* halo1_obs;   // the window whose halo halo1[par] holds (null: none)
@@ -89,14 +52,7 @@ struct pmenv {
     bool device_seq;
     int32_t* seq;         // {D, C, V, pad, HOBS lo, HOBS hi} (step_flat.h)
     uint64_t snap_stride; // bytes between the two parities of the snapshot / halo
-    // one launch, scalar blocks relaying w' and the counter to the stream tiles (step_relay.h)
-    bool relay_ok;        // the shape fits step_relay_kernel
-    int relay_auto;       // PMENV_FUSE_* bits the automatic choice gives it
-    int relay;            // PMENV_FUSE_* bits: which windows take it now
-    int relay_kl, relay_ka;   // the scalar step's form: KL lanes per env, KA strided assets per lane (0: register)
-    int relay_block, relay_v; // the tiles' geometry: relay_block threads x relay_v 16-B chunks
-    int relay_epb;        // envs per scalar block (relay_block / 64 waves x 64 / relay_kl envs)
-    uint32_t relay_tiles, relay_scal;
+    // the relay step's memory and sequencing (step_relay.h)
     void* relay_mem;      // control words | relay words, deferral list, tile claims | counter copy x 2 | halo x 2 (allocated when
                           // AUTO gives the shape the relay step or pmenv_set_step_path asks for it)
     uint32_t* relay_seq;  // device-sequenced words {D, E, V, C, EC, pad, HOBS lo, HOBS hi} (step_relay.h)
@@ -129,16 +85,11 @@ struct pmenv {
     bool dev_pending;     // an asynchronous call of this handle since its last synchronous host call
     pmenv_dev::StepParams res_p;   // its launch arguments
     pmenv_dev::HostIO res_io;
-    int path;             // pmenv_step_path_kind
     void* tools;        // tools build: its knob state (null in the product library)
     char err[512];
 };
 
 namespace pmenv_host {
-
-constexpr int PMENV_FUSE_DB = 1, PMENV_FUSE_INPLACE = 2;
-constexpr int kOneV = 4;              // step_env_kernel: 16-B chunks per lane
-constexpr int kK1Str = 100000;        // k1_vec: the strided layout of scalar_step_vec_kernel
 
 inline void set_err(pmenv* h, const char* fmt, ...) {
     if (!h) return;
@@ -200,12 +151,6 @@ inline int device_cus() {
     return cus;
 }
 
-// the relay step's deferral list ({epoch, count} + one entry per tile) and tile claims, 16-B padded
-inline size_t relay_list_bytes(const pmenv* h) {
-    const size_t tiles = h->relay_tiles;
-    return ((tiles + 1) * 8 + 15) / 16 * 16 + (tiles * 4 + 15) / 16 * 16;
-}
-
 inline int check_launch(pmenv* h, const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -213,69 +158,6 @@ inline int check_launch(pmenv* h, const char* what) {
         return PMENV_ERR_HIP;
     }
     return PMENV_OK;
-}
-
-// Geometry of the row-kernel stream (the fallback of the flat stream): units of R whole
-// asset rows per `block`-thread workgroup, R*W*F floats <= 4*block*V (V float4 per
-// thread) and R*W*F % 4 == 0 so every unit starts 16-B aligned. `v_order` lists V in
-// preference order; want_rows > 0 forces R (tools A/B). Returns false when the shape
-// needs the LDS fallback.
-inline bool plan_streaming(const pmenv_cfg& c, const int* v_order, int block, int want_rows, int* unit_rows,
-                           int* vec_per_thread) {
-    const int64_t WF = (int64_t)c.window * c.features;
-    if (c.features != 5 || ((int64_t)c.num_assets * WF) % 4 != 0) return false;
-    int align = 1;                       // rows per unit must be a multiple of this
-    while ((align * WF) % 4 != 0) ++align;
-    static const int kAscending[3] = {1, 2, 4};
-    if (want_rows > 0) v_order = kAscending;   // a forced unit takes the fewest float4 per thread that hold it
-    for (int vi = 0; vi < 3; ++vi) {
-        const int V = v_order[vi];
-        const int64_t cap = (int64_t)block * 4 * V;
-        int R = (int)(cap / WF);
-        if (R >= c.num_assets) R = c.num_assets;
-        else R -= R % align;
-        if (R < 1 || (int64_t)R * WF > cap) continue;
-        if (want_rows > 0) {
-            if (want_rows > R) continue;
-            if (want_rows != c.num_assets && want_rows % align) return false;
-            R = want_rows;
-        }
-        *unit_rows = R;
-        *vec_per_thread = V;
-        return true;
-    }
-    return false;
-}
-
-// The one-workgroup-per-env step with V chunks per lane: waves per workgroup and whether
-// the shape fits (F = 5, W >= 2, N <= 64: the scalar step on one wave; the env's 1 KiB
-// blocks in at most 16 waves and 64 KiB of LDS)
-inline void plan_one(pmenv* h, int V) {
-    const pmenv_cfg& c = h->cfg;
-    const int64_t per = (int64_t)c.num_assets * c.window * c.features;
-    // the env's chunks start anywhere in a 64-chunk block: up to 63 slots ahead of it
-    const uint32_t blocks = (h->per4 + 63u + 63u) / 64u;
-    h->one_waves = (int)((blocks + (uint32_t)V - 1) / (uint32_t)V);
-    h->one_ok = h->streaming && c.features == 5 && c.window >= 2 && c.num_assets <= 64 && per % 4 == 0 &&
-                h->one_waves <= 16 && ((int64_t)64 * V * h->one_waves + 2) * 16 <= 65536;
-}
-
-// The flat one-launch step in `block` x `vec` tiles: the flat stream's shape rules, at
-// most one env per wave in a tile, N <= 64 — or, for wide envs (64 < N <= 512,
-// step_flat_vec_kernel), the rows a tile touches per env within one wave's 64 staged bar
-// rows (W >= 14 at F = 5 for 16 KiB tiles)
-inline bool flat1_fits(const pmenv* h, int block, int vec) {
-    const pmenv_cfg& c = h->cfg;
-    const int64_t WF = (int64_t)c.window * c.features;
-    const uint32_t cpw = (uint32_t)(block * vec);
-    const uint32_t ne_max = h->per4 ? (cpw + h->per4 - 2u) / h->per4 + 1u : 0u;
-    const int64_t span_rows = (4ll * cpw - 1) / (WF > 0 ? WF : 1) + 2;
-    const bool wide_ok = c.num_assets <= pmenv_dev::kWideMaxAssets && span_rows <= 64;
-    return h->flat_ok && (c.num_assets <= 64 || wide_ok) && ne_max <= (uint32_t)(block / 64);
-}
-
-inline int64_t window_bytes(const pmenv_cfg& c) {
-    return (int64_t)c.num_envs * c.num_assets * c.window * c.features * 4;
 }
 
 }  // namespace pmenv_host

@@ -5,7 +5,8 @@
 // fallbacks), scalar_vec.h (packed scalar step), data.h (synthetic market data),
 // rollout.h (GAE, moments), replay.h (replay gather, metrics), metrics_env.h (the metrics
 // per episode) and trainer.h (batched reward); the step's launchers in launch.h, the
-// handle and its shape planning in handle.h, the sample gathers' kernel choice in replay_plan.h.
+// handle in handle.h, its shape plan — which kernel a step takes, in which geometry — in
+// step_plan.h, the sample gathers' kernel choice in replay_plan.h (both host only).
 //
 // Every entry point enqueues on the caller's stream and never synchronises, allocates or
 // frees (graph-capturable), except create / destroy / the explicit synchronous queries
@@ -35,6 +36,7 @@
 #include "replay_valid.h"
 #include "replay_plan.h"
 #include "rollout.h"
+#include "step_plan.h"
 #include "trainer.h"
 
 using namespace pmenv_dev;
@@ -43,27 +45,6 @@ using namespace pmenv_host;
 namespace {
 
 thread_local char g_create_err[512] = "";
-
-// K1 shape per asset count: N <= 64 keeps one asset per lane, with reductions bitwise
-// those of the one-launch steps' scalar part (so the paths, and sharded and unsharded
-// runs whose path can differ by env count, give the same bits): N <= 16 the packed form
-// with 8 / 16 lanes per env (8 / 4 envs per wave instead of 2; its butterfly pairs the
-// lanes as the row shifts do, every pair sum commutes bitwise, and the all-zero padding
-// lanes of the register form only add +0.0, which the packed form's 0.0 + x seed
-// reproduces), 16 < N <= 64 the register form; 64 < N <= 512 the packed strided form
-// (64 lanes x A assets, every dword load a coalesced run; step_flat_vec_kernel shares
-// it); N > 512 the LDS form.
-int pick_k1_vec(const pmenv_cfg& c) {
-    const int N = c.num_assets;
-    if ((int64_t)c.num_envs * N * 4 >= (1ll << 32)) return 0;     // descriptors span the [B*N] arrays
-    if (N <= 8) return kK1Str + 801;
-    if (N <= 16) return kK1Str + 1601;
-    if (N <= 64) return 0;
-    if (N <= 128) return kK1Str + 6402;
-    if (N <= 256) return kK1Str + 6404;
-    if (N <= 512) return kK1Str + 6408;
-    return 0;
-}
 
 // calls f(std::integral_constant<int, V>()) for the V among Vs that equals v: a planned
 // pairs-per-thread or store-policy value becomes a kernel's template argument
@@ -154,12 +135,9 @@ int flat1_invalidate(pmenv* h, hipStream_t stream, int what = kInvalSnap | kInva
 // one memset clears all three when the eager epoch wraps.
 int relay_alloc(pmenv* h) {
     if (h->relay_mem || !h->relay_ok) return PMENV_OK;
-    const pmenv_cfg& c = h->cfg;
-    const uint64_t B = (uint64_t)c.num_envs, BN = B * (uint64_t)c.num_assets;
-    auto up16 = [](size_t x) { return (x + 15) / 16 * 16; };
-    const size_t ctl_b = 64, words_b = up16(BN * 8) + relay_list_bytes(h), kp_b = up16(B * 4);
-    const size_t hal = up16((size_t)h->relay_tiles * 32);
-    const size_t bytes = ctl_b + words_b + 2 * kp_b + 2 * hal;
+    const size_t BN = (size_t)h->cfg.num_envs * (size_t)h->cfg.num_assets;
+    const size_t ctl_b = 64, words_b = h->relay_words_bytes, kp_b = h->relay_kp_bytes, hal = h->relay_halo_bytes;
+    const size_t bytes = h->relay_bytes;
     DeviceGuard g(h->device);
     void* m = nullptr;
     hipError_t ae = hipMalloc(&m, bytes);
@@ -187,30 +165,6 @@ int relay_alloc(pmenv* h) {
     h->relay_par = 0;
     h->relay_epoch = 0;
     return PMENV_OK;
-}
-
-// which windows take the one-launch steps under `path`
-int one_bits(const pmenv* h, int path) {
-    if (path == PMENV_STEP_PATH_ONE_LAUNCH) return h->one_ok ? (PMENV_FUSE_DB | PMENV_FUSE_INPLACE) : -1;
-    if (path == PMENV_STEP_PATH_TWO_LAUNCH) return h->streaming || h->gen_ok ? 0 : -1;
-    if (path == PMENV_STEP_PATH_FLAT) return h->flat1_ok ? 0 : -1;
-    if (path == PMENV_STEP_PATH_RELAY) return h->relay_ok ? 0 : -1;
-    return h->one_auto;
-}
-int relay_bits(const pmenv* h, int path) {
-    if (path == PMENV_STEP_PATH_RELAY) return h->relay_ok ? (PMENV_FUSE_DB | PMENV_FUSE_INPLACE) : -1;
-    if (path == PMENV_STEP_PATH_AUTO) return h->relay_auto;
-    return 0;
-}
-int gen_bits(const pmenv* h, int path) {
-    if (path == PMENV_STEP_PATH_TWO_LAUNCH) return h->gen_ok ? (PMENV_FUSE_DB | PMENV_FUSE_INPLACE) : 0;
-    if (path == PMENV_STEP_PATH_AUTO) return h->gen_auto;
-    return 0;
-}
-int flat1_bits(const pmenv* h, int path) {
-    if (path == PMENV_STEP_PATH_FLAT) return h->flat1_ok ? (PMENV_FUSE_DB | PMENV_FUSE_INPLACE) : -1;
-    if (path == PMENV_STEP_PATH_AUTO) return h->flat1_auto;
-    return 0;
 }
 
 }  // namespace
@@ -294,271 +248,13 @@ int pmenv_create_in(const pmenv_cfg* cfg, int device, void* state, size_t state_
         free(h);
         return code;
     };
-    if (c.num_envs < 1 || c.num_assets < 1 || c.window < 1 || c.features < 2) {
-        set_err(h, "invalid shape B=%d N=%d W=%d F=%d (need B,N,W >= 1, F >= 2)", c.num_envs, c.num_assets,
-                c.window, c.features);
-        return fail(PMENV_ERR_ARG);
-    }
-    if (c.close_channel < 0 || c.close_channel >= c.features - 1) {
-        set_err(h, "close_channel %d must be a market channel in [0, F-2]", c.close_channel);
-        return fail(PMENV_ERR_ARG);
-    }
-    if (c.reward_kind < 0 || c.reward_kind > 3 || c.norm_mode < 0 || c.norm_mode > 1 || c.ring_mode < 0 ||
-        c.ring_mode > 1 || c.ret_mode < 0 || c.ret_mode > 2 || c.mu_max_iter < 0 || !(c.commission >= 0.0) ||
-        !(c.commission < 1.0)) {
-        set_err(h, "invalid mode/commission value in cfg");
-        return fail(PMENV_ERR_ARG);
-    }
+    // the shape plan (step_plan.h): the argument checks and every kernel choice; the tools
+    // build's PMENV_* knobs rewrite it before the sizes that follow from it are taken
+    if (const int rc = step_plan(c, h, h->err, sizeof(h->err))) return fail(rc);
     if (h->cfg.ret_mode == PMENV_RET_AUTO)
         h->cfg.ret_mode = c.reward_kind == PMENV_REWARD_LOG_RETURN ? PMENV_RET_GROSS : PMENV_RET_NET;
-    const int64_t WF = (int64_t)c.window * c.features;
-    if (WF > kTileFloats) {
-        set_err(h, "window*features = %lld exceeds the %d-float LDS tile", (long long)WF, kTileFloats);
-        return fail(PMENV_ERR_ARG);
-    }
-    if ((int64_t)c.num_assets * WF >= (1ll << 31)) {
-        set_err(h, "per-env obs block too large");
-        return fail(PMENV_ERR_ARG);
-    }
-    // LDS fallback tile geometry: whole asset rows, 16-B granular when every env block is
-    int R = (int)(kTileFloats / WF);
-    if (R > c.num_assets) R = c.num_assets;
-    bool vec = ((int64_t)c.num_assets * WF) % 4 == 0;
-    if (vec && R < c.num_assets) {
-        while (R > 0 && ((int64_t)R * WF) % 4 != 0) --R;
-        if (R == 0) { vec = false; R = (int)(kTileFloats / WF); }
-    }
-    h->rows_per_tile = R;
-    h->vec = vec;
-    // the register step: the env's window within BLOCK x E floats (one workgroup per env)
-    {
-        const int64_t nwf = (int64_t)c.num_assets * WF;
-        h->small_block = nwf <= 256 * 16 ? 256 : nwf <= 512 * 16 ? 512 : nwf <= 1024 * 16 ? 1024 : 0;
-        h->small_e = nwf <= 256 * 8 ? 8 : 16;
-        // config 1's 1 x 5 x 50 x 5: 4.1 us (step_small_kernel) -> see DESIGN.md §3
-        // (step_tiny_kernel stages the day's bar two floats per thread: N (F - 1) <= 2 x 256)
-        h->tiny = h->small_block == 256 && h->small_e == 8 && c.num_assets <= 64 &&
-                  (int64_t)c.num_assets * (c.features - 1) <= 2 * 256;
-    }
-    // surface steps on windows past the Infinity Cache with 16-B granular env blocks: the scalar
-    // step, then surface_stream_kernel (65,536 x 30 x 50 x 5 723 us with the ring columns staged
-    // in LDS, against 939 on the per-env kernel's dword writes, 892 with its writes in whole
-    // chunks; cache-resident windows keep the per-env kernel: 4,096 x 30 38.3 against 48.6 in
-    // whole chunks — ab_r05/surface_stream_r05s4_*, surface_ringlds_r05sr.*); the staged
-    // columns (rows x W floats) and counters (rows) within 64 KiB
-    h->surf_lds = (size_t)(4 * 1024 / WF + 2) * (c.window + 1) * 4;   // + each row's counter
-    h->surf_stream = window_bytes(c) > (256ll << 20) && ((int64_t)c.num_assets * WF) % 4 == 0 &&
-                     (int64_t)c.num_envs * ((int64_t)c.num_assets * WF / 4) < (1ll << 31) - 1024 &&
-                     h->surf_lds <= (64u << 10) && 4 * 1024 / WF + 2 <= 256;   // a thread per row's counter
-    h->tile_floats = (int)((((int64_t)R * WF) + 3) / 4 * 4);
-    h->lds_tile = scratch_bytes(h->tile_floats, c.num_assets, c.features);
-    h->lds_surface = scratch_bytes(0, c.num_assets, c.features);
-
-    // ---- the two-launch stream: row-kernel geometry (fallback) and the flat stream
-    static const int kInplaceOrder[3] = {2, 4, 1}, kDoubleOrder[3] = {4, 2, 1};
-    h->streaming = plan_streaming(c, kInplaceOrder, kStreamBlock, 0, &h->unit_rows, &h->stream_vec) &&
-                   plan_streaming(c, kDoubleOrder, kStreamBlock, 0, &h->unit_rows_db, &h->stream_vec_db);
-    const int64_t per = (int64_t)c.num_assets * c.window * c.features;
-    const int64_t win = window_bytes(c);
-    // Flat 16-B stream (F = 5, W >= 2, 16-B granular envs, chunk count < 2^31) in place
-    // (with the halo) and double-buffered: 512 threads x 2 chunks, side data through the
-    // scalar unit (6.38 TB/s against 5.37 for whole-row units).
-    h->flat_ok = h->streaming && c.features == 5 && c.window >= 2 && per % 4 == 0 &&
-                 (int64_t)c.num_envs * (per / 4) < (1ll << 31) - 1024;
-    h->flat = h->flat_inplace = h->flat_ok;
-    // in place, cache-resident windows (<= 256 MiB) take 8 KiB workgroups: 80.2 vs 83.2 us
-    // at 8,192 x 30, 44.4 vs 44.7 at 4,096 (profiles/ab_r02/r02w_smallip_*); above, 16 KiB
-    // (round 1: 512 x 2 against 256 x 1 / 2 / 4, 512 x 1, 1024 x 1)
-    h->flat_ip_block = win <= (256ll << 20) ? 256 : 512;
-    h->flat_ip_vec = 2;
-    h->flat_qtot = h->flat_ok ? (uint32_t)((int64_t)c.num_envs * (per / 4)) : 0u;
-    // nt unless the stream's working set fits the 256 MiB Infinity Cache: the window in
-    // place (<= 256 MiB), the window and its double buffer otherwise (<= 128 MiB each).
-    // Step at 4,096 x 30 x 50 x 5 (123 MB) 44.4 us with the default policy against 46.5
-    // nt; 8,192 envs (246 MB) in place 84.6 / 86.1 but double-buffered 91.2 / 86.5;
-    // 16,384: 199.6 / 164.6 (profiles/ab_r01/pol_small_r01j.log, pol_ip_r01m.log)
-    h->flat_pol = win <= (128ll << 20) ? 0 : 1;
-    h->flat_ip_pol = win <= (256ll << 20) ? 0 : 1;
-    h->k1_vec = pick_k1_vec(c);
-    h->per4 = (uint32_t)(per / 4);
-
-    // ---- the one-launch step (step_env_kernel, one workgroup per env): F = 5, W >= 2,
-    // N <= 64 (the scalar step on one wave), 16-B granular env windows whose 1 KiB
-    // blocks fit 16 waves and 64 KiB of LDS, 4 chunks per lane (650 us against 662-666
-    // for 8, 762 for 3, 860 for 2 at the BASELINE shape). AUTO gives it the windows of at
-    // most 48 MiB, where launch latency dominates and it wins by 7-38 % (tools/gpu_ab_smallb.sh,
-    // profiles/ab_r02/r02u_*: N = 8..64, 256..4,096 envs; N = 30: 64 envs 6.5 vs 9.6 us,
-    // 1,024: 13.1 vs 18.2). Larger windows take the two-launch stream: its fixed 16 KiB
-    // workgroups run 640-670 us on a 2 GB window at every asset count measured, while the
-    // one-workgroup-per-env geometry ties it only at N = 30 (650-658 us) and loses 4-15 %
-    // at N = 8, 16, 24, 32, 40, 48, 60, 64 (profiles/ab_r02/r02r_*, r02s_*, r02t_*).
-    // (Also beyond the flat stream's 2^31-chunk index, where the two-launch path would
-    // fall back to the whole-row stream.)
-    plan_one(h, kOneV);
-    h->one_auto = h->one_ok && (win <= (48ll << 20) || !h->flat_inplace) ? (PMENV_FUSE_DB | PMENV_FUSE_INPLACE) : 0;
-
-    // ---- the one-launch flat step (step_flat_kernel; step_flat_vec_kernel for 64 < N <=
-    // 512): the flat stream's shape rules, the scalar step on one wave per env, at most one
-    // env per wave in a tile (flat1_fits). Geometry: 256 threads x 4 chunks (16 KiB tiles,
-    // 4 waves) where env windows have >= 511 chunks, 512 x 2 (8 waves) from 148 chunks.
-    // 256 x 4 against 512 x 2 / 512 x 4 / 1024 x 2 / 256 x 8 / 256 x 2 / 128 x 8 / 128 x 4 at
-    // 65,536 x 30 in place: 629.5 against 714 / 678 / 790 / 695 / 675 / 624 / 641 us; 128 x 8
-    // loses 15 % at N = 16 and 64 where 256 x 4 wins (profiles/ab_r02/r02w_flat1b_*,
-    // r02w_flat1c_*). A persistent form that keeps the next tile's loads in flight needs
-    // 160 VGPRs (3 waves per SIMD): 2x slower.
-    // 128 x 8 (2 waves, 8 chunks per lane, the same 16 KiB tiles) where every tile holds at
-    // most two envs (1,023 .. 1,999 chunks per env: N = 20 .. 39 at W = 50) and the window
-    // streams through HBM: 0.5-1.1 % ahead of 256 x 4 from 49,152 envs at N = 30 (65,536:
-    // 625.7 vs 629.4 and 628.8 vs 631.6 us; 98,304: 941.1 vs 951.6), N = 20 / 24 / 28 by
-    // 1.0 / 0.7 / 0.5 %; behind it at 16,384 envs (162.9 vs 161.4) and at N = 16 / 64
-    // (profiles/ab_r02/r02w_flat1k_*, r02w_flat1l_*, r02w_flat1c_*). Wide envs: 256 x 4.
-    const bool band128 = c.num_assets <= 64 && h->per4 >= 1023u && h->per4 < 2000u && win > (1ll << 30);
-    if (band128 && flat1_fits(h, 128, 8)) { h->flat1_block = 128; h->flat1_vec = 8; }
-    else if (flat1_fits(h, 256, 4)) { h->flat1_block = 256; h->flat1_vec = 4; }
-    else { h->flat1_block = 512; h->flat1_vec = 2; }
-    h->flat1_ok = flat1_fits(h, h->flat1_block, h->flat1_vec) && (c.num_assets <= 64 || h->flat1_block == 256);
-    // AUTO: above the one-launch-per-env windows (48 MiB) the flat step beats the two-launch
-    // stream by 1-3.5 % for env windows of >= 1,000 chunks (N >= 16 at W = 50): 65,536 x 30
-    // 629.5 / 639.7 against 642.4 / 648.8 us on two boxes, N = 24 / 40 / 48 / 64 by 1-3.4 %,
-    // N = 16 681 vs 689; it loses at N = 8 (500 chunks, 4 envs per tile: 713 vs 691) and in
-    // place on cache-resident windows (4,096 envs: 46.3 vs 44.2 us, 8,192: 85.2 vs 84.2);
-    // double-buffered it wins from 2,048 envs (25.4 vs 27.0) (profiles/ab_r02/r02w_flat1d_*).
-    // Commission > 0: every tile an env straddles runs the capped fixed point. With the
-    // active-set iteration (scalar_core), a uniform wave index (no waterfall loops around
-    // the scalar loads) and the reciprocal of 1 - c w0, the flat step leads there too:
-    // 65,536 x 30 at 0.0025 642.8 vs 661.9 us on two launches (profiles/ab_r03/comm3_r03.err;
-    // in round 2 the fixed point cost it 6-8 %: 701 vs 662).
-    h->flat1_auto = 0;
-    if (h->flat1_ok && c.num_assets <= 64 && h->flat1_block <= 256 && h->per4 >= 1000u) {
-        if (win > (48ll << 20)) h->flat1_auto |= PMENV_FUSE_DB;
-        if (win > (256ll << 20)) h->flat1_auto |= PMENV_FUSE_INPLACE;
-        h->one_auto &= ~h->flat1_auto;
-    }
-    // Wide envs (step_flat_vec_kernel, 64 < N <= 512): every tile an env straddles runs the
-    // env's whole packed scalar step, which costs more than the kernel boundary it saves
-    // from 4 assets per lane on: 8,192 x 500 in place 1,512 (128 x 8) / 1,605 (256 x 4)
-    // against 1,381 us on two launches, 2,048 x 200 143.5 vs 140.0; at 2 assets per lane
-    // it wins on HBM-streamed windows: 16,384 x 100 532.9 vs 549.7 us (profiles/ab_r03/
-    // wide_r03wide.err). AUTO gives it in-place windows > 1 GiB at N <= 128 without commission.
-    if (h->flat1_ok && c.num_assets > 64 && c.num_assets <= 128 && win > (1ll << 30) && !(c.commission > 0.0))
-        h->flat1_auto |= PMENV_FUSE_INPLACE;
-    // In place, 24-100 MiB: a one-launch step beats the two-launch stream there (round 3,
-    // in-process interleaved, profiles/ab_r03/band_r03u.err, band_r03w.err; µs per step,
-    // two launches / one WG per env / flat step): N = 30 at 2,048 envs 27.2 / 24.7 / 25.9,
-    // 3,072 36.3 / 34.7 / 36.3; N = 16 at 4,096 28.8 / 28.1 / 26.8, 6,144 38.1 / 39.8 / 36.9;
-    // N = 8 at 4,096 19.4 / 18.9 / 16.3, 8,192 29.1 / 30.5 / 27.2; N = 32 at 3,072 37.9 /
-    // 38.4 / 36.7; N = 64 at 1,024 28.6 / - / 26.8. From ~115 MiB the two-launch stream
-    // leads (N = 30 at 4,096 44.8 / 45.7 / 47.2, N = 32 / 16 / 8 at 125 MiB, N = 48 at 188).
-    // Which one-launch form: the one-WG-per-env step where its waves' chunk slots hold the
-    // env with >= 90 % occupancy (N = 30: 1,875 of 2,048; it wins by 5-8 % there), else
-    // the flat step (N = 8 / 16 / 32: 65 / 78 / 87 %, the flat step wins by 4-14 %) — the
-    // same rule from 24 MiB, where the flat step also wins at N = 8 and 16 (4,096 x 8:
-    // 16.3 vs 18.9 us; 3,072 x 16: 21.6 vs 22.6).
-    if (win > (24ll << 20) && win <= (100ll << 20)) {
-        const double one_fill = h->one_ok ? (double)h->per4 / (256.0 * h->one_waves) : 0.0;
-        if (h->one_ok && one_fill >= 0.9) {
-            h->one_auto |= PMENV_FUSE_INPLACE;
-        } else if (h->flat1_ok && c.num_assets <= 64) {
-            h->flat1_auto |= PMENV_FUSE_INPLACE;
-            h->one_auto &= ~PMENV_FUSE_INPLACE;
-        } else if (h->one_ok) {
-            h->one_auto |= PMENV_FUSE_INPLACE;
-        }
-    }
-
-    // ---- the relayed one-launch step (step_relay_kernel): the flat stream's shapes (F = 5,
-    // W >= 2, 16-B granular env windows) with the two-launch path's scalar step forms
-    // (N <= 512, the packed forms' [B*N] descriptors under 2^32 bytes), the stream's tile
-    // geometry; at most BLOCK rows per tile (4 * 2 <= W * F).
-    {
-        const int N = c.num_assets;
-        const int kv = h->k1_vec >= kK1Str ? h->k1_vec - kK1Str : h->k1_vec;
-        h->relay_block = h->flat_ip_block;
-        h->relay_v = 2;
-        // a tile stages one row per thread: 4 CPW / (W F) + 2 rows must fit its BLOCK threads
-        // (for V = 2: W >= 2; the host schedule emulation under tests/ checks it per tile)
-        const bool rows_fit = 4 * h->relay_block * h->relay_v / (c.window * 5) + 2 <= h->relay_block;
-        h->relay_ok = h->flat_ok && c.window >= 2 && rows_fit && N <= 512 && (N <= 64 || h->k1_vec != 0);
-        h->relay_kl = kv ? kv / 100 : (N <= 32 ? 32 : 64);
-        h->relay_ka = kv ? kv % 100 : 0;
-        h->relay_auto = 0;
-    }
-    // AUTO gives the relay step the cache-resident windows where the kernel boundary of two
-    // launches, or the scalar step inside every tile, is what a step pays for (N <= 64,
-    // round 4, in-process interleaved, profiles/ab_r04/relay_band_r04b.err; us per step,
-    // AUTO's previous choice / relay): in place 24-256 MiB — N = 30 at 2,048 / 3,072 / 4,096 /
-    // 6,144 / 8,192 envs 24.9 / 23.7, 34.5 / 32.1, 44.3 / 40.6, 62.1 / 58.3, 81.9 / 80.0 (with
-    // commission 83.6 / 80.6), N = 8 at 4,096 / 8,192 / 16,384 16.2 / 14.5, 27.7 / 24.3, 46.4 /
-    // 42.7, N = 16 at 4,096 / 8,192 27.6 / 24.4, 46.4 / 42.4, N = 64 at 2,048 / 4,096 46.6 /
-    // 43.1, 85.9 / 84.3 — except 24-48 MiB where the one-workgroup-per-env step holds the env
-    // at >= 90 % (1,024 x 30: 13.5 / 14.9); double-buffered 48-128 MiB (2,048 / 4,096 x 30:
-    // 27.2 / 23.2, 49.1 / 41.6; 8,192: 83.2 / 90.6). From 256 MiB in place the flat step leads
-    // (12,288 / 16,384 / 65,536 x 30: 119.0 / 120.5, 156.8 / 159.9, 625.5 / 641.7), and at
-    // config 5 two launches (1,324.6 / 1,360.3).
-    if (h->relay_ok && c.num_assets <= 64) {
-        const double one_fill = h->one_ok ? (double)h->per4 / (256.0 * h->one_waves) : 0.0;
-        const bool one_holds = h->one_ok && one_fill >= 0.9 && win <= (48ll << 20);
-        if (win > (24ll << 20) && win <= (256ll << 20) && !one_holds) h->relay_auto |= PMENV_FUSE_INPLACE;
-        if (win > (48ll << 20) && win <= (128ll << 20)) h->relay_auto |= PMENV_FUSE_DB;
-        h->one_auto &= ~h->relay_auto;
-        h->flat1_auto &= ~h->relay_auto;
-        // 256 x 4 tiles (16 KiB) for the largest cache-resident in-place windows, 192-256 MiB,
-        // with the register-form scalar step of 17 <= N <= 32: config 4's 8-GPU share, 8,192 x
-        // 30 in place, 78.6 vs 81.5 us (profiles/r06/relay_stamps/geom_8192x30.err; round 4: 76.8
-        // vs 79.5 and 77.5 vs 78.1, ab_r04/relay_geom*); at 4,096 x 30 (123 MB) they lose
-        // (42.3 vs 41.1), so 256 x 2 stays below
-        const bool rows_fit4 = 4 * 256 * 4 / (c.window * 5) + 2 <= 256;
-        if ((h->relay_auto & PMENV_FUSE_INPLACE) && win > (192ll << 20) && h->relay_block == 256 &&
-            h->relay_kl == 32 && h->relay_ka == 0 && rows_fit4)
-            h->relay_v = 4;
-    }
-    // ---- the generic stream (advance_gen_kernel, F != 5): 2 <= F <= 16 (its halo is the two
-    // chunks past a workgroup, four past F = 8), 16-B granular env windows, at most BLOCK rows
-    // per workgroup.
-    // AUTO gives it every window above 2 MiB (16 MiB where step_tiny_kernel would take it),
-    // both modes: against the register step / the LDS fallback, one process, the same bits
-    // (profiles/ab_r05/gen_few_r05gf2.*), 64 / 256 x 30 x 50 x 8 in place 9.2 / 11.2 against
-    // 12.8 / 14.2 us, 128 x 30 x 50 x 3 8.7 vs 9.2, 32 x 64 x 50 x 8 8.6 vs 16.4, 64 x 100 x 50 x 8
-    // 10.9 vs 24.4 (LDS fallback), 2,048 x 128 x 50 x 4 double-buffered 76.8 vs 91.8; ties at 1-2
-    // MiB (128 x 16 x 32 x 8 8.9 / 8.9, 64 x 16 x 32 x 8 9.0 vs 8.8); over tiny windows 1,024 x 5 x
-    // 50 x 8 (8 MiB) 9.9 vs 7.8, 4,096 x 5 x 50 x 8 17.1 / 17.0, 4,096 x 8 x 32 x 6 14.9 vs 16.7
-    {
-        const int F = c.features;
-        // 512 x 2 chunks per workgroup for windows past 128 MiB, 256 x 2 below (gen_geom_*_r05gg.*,
-        // against 256 x 4: 65,536 x 30 x 50 x 8 in place / double-buffered 1,015.5 / 1,033.2 vs
-        // 1,061.6 / 1,069.0 us, F = 3 / 4 388.8 / 514.9 vs 406.9 / 537.4, 16,384 x 30 x 50 x 8
-        // 254.1 vs 268.3; within 2 % of 256 x 2 at 4,096 envs and below)
-        h->gen_block = win > (128ll << 20) ? 512 : 256;
-        h->gen_v = 2;
-        const int64_t cpw = 1024;                           // the shape rule at the larger tile
-        h->gen_ok = F != 5 && F >= 2 && F <= 16 && per % 4 == 0 &&
-                    (int64_t)c.num_envs * (per / 4) < (1ll << 31) - 1024 && 4 * cpw / WF + 2 <= 256;
-        h->gen_qtot = h->gen_ok ? (uint32_t)((int64_t)c.num_envs * (per / 4)) : 0u;
-        h->gen_auto = h->gen_ok && win > (h->tiny ? (16ll << 20) : (2ll << 20)) ? (PMENV_FUSE_DB | PMENV_FUSE_INPLACE) : 0;
-    }
-    pmenv_tools::plan(h);     // the tools build's PMENV_* knobs (nothing in the product library)
-    if (h->streaming) {
-        h->units_per_env = (c.num_assets + h->unit_rows - 1) / h->unit_rows;
-        h->units_per_env_db = (c.num_assets + h->unit_rows_db - 1) / h->unit_rows_db;
-    }
-    h->path = PMENV_STEP_PATH_AUTO;
-    h->one = h->one_auto;
-    h->flat1 = h->flat1_auto;
-    h->relay = h->relay_ok ? h->relay_auto : 0;
-    h->gen = h->gen_ok ? h->gen_auto : 0;
-
-    h->scalar_scratch_floats = (int)((scratch_bytes(0, c.num_assets, c.features) / 4 + 3) / 4 * 4);
-    h->lds_scalar = (size_t)kScalarWaves * h->scalar_scratch_floats * 4;
-    if (h->lds_tile > 160 * 1024 || h->lds_scalar > 160 * 1024) {
-        set_err(h, "num_assets %d needs more than 160 KiB of LDS", c.num_assets);
-        return fail(PMENV_ERR_ARG);
-    }
-    if ((int64_t)c.num_envs * (h->streaming ? (h->units_per_env > h->units_per_env_db ? h->units_per_env
-                                                                                    : h->units_per_env_db)
-                                               : 1) >= (1ll << 31)) {
-        set_err(h, "too many envs for one launch");
-        return fail(PMENV_ERR_ARG);
-    }
+    pmenv_tools::plan(h);     // nothing in the product library
+    if (const int rc = step_plan_finish(h, c, h->err, sizeof(h->err))) return fail(rc);
 
     DeviceGuard g(device);
     size_t off[PMENV_STATE_FIELDS];
@@ -580,13 +276,8 @@ int pmenv_create_in(const pmenv_cfg* cfg, int device, void* state, size_t state_
         }
         h->owns_state = true;
     }
-    if (h->flat_inplace || h->gen_ok) {
-        const uint32_t cpw = (uint32_t)(h->flat_inplace ? h->flat_ip_block * h->flat_ip_vec : h->gen_block * h->gen_v);
-        const uint32_t qtot = h->flat_inplace ? h->flat_qtot : h->gen_qtot;
-        const uint32_t wgs = (qtot + cpw - 1) / cpw;
-        h->halo_wgs = wgs > 0 ? wgs - 1 : 0;
-        const size_t per_wg = !h->flat_inplace && c.features > 8 ? 64 : 32;   // four chunks past F = 8
-        hipError_t ae = hipMalloc(&h->halo, (size_t)(h->halo_wgs + 1) * per_wg);
+    if (h->halo_bytes) {
+        hipError_t ae = hipMalloc(&h->halo, h->halo_bytes);
         if (ae != hipSuccess) {
             set_err(h, "hipMalloc(halo) failed: %s", hipGetErrorString(ae));
             h->halo = nullptr;
@@ -596,13 +287,8 @@ int pmenv_create_in(const pmenv_cfg* cfg, int device, void* state, size_t state_
     if (h->flat1_ok) {
         // two parities of the snapshot (16-B aligned fields) and of the tile halo
         const size_t B = (size_t)c.num_envs, BN = B * (size_t)c.num_assets;
-        auto up16 = [](size_t x) { return (x + 15) / 16 * 16; };
-        const size_t one = up16(B * 8) + up16(B * 4) + 2 * up16(BN * 4);
-        const uint32_t cpw = (uint32_t)(h->flat1_block * h->flat1_vec);
-        const uint32_t wgs = (h->flat_qtot + cpw - 1) / cpw;
-        h->halo1_wgs = wgs > 0 ? wgs - 1 : 0;
-        const size_t hal = up16(((size_t)h->halo1_wgs + 1) * 32);
-        hipError_t ae = hipMalloc(&h->snap, 2 * (one + hal) + 64);
+        const size_t one = h->snap_state_bytes, hal = h->snap_halo_bytes;
+        hipError_t ae = hipMalloc(&h->snap, h->snap_bytes);
         if (ae != hipSuccess) {
             set_err(h, "hipMalloc(snapshot) failed: %s", hipGetErrorString(ae));
             h->snap = nullptr;
@@ -623,13 +309,7 @@ int pmenv_create_in(const pmenv_cfg* cfg, int device, void* state, size_t state_
             return fail(PMENV_ERR_HIP);
         }
     }
-    if (h->relay_ok) {
-        const uint32_t cpw = (uint32_t)(h->relay_block * h->relay_v);
-        h->relay_epb = (h->relay_block / 64) * (64 / h->relay_kl);
-        h->relay_tiles = (h->flat_qtot + cpw - 1) / cpw;
-        h->relay_scal = (uint32_t)(((uint64_t)c.num_envs + (uint64_t)h->relay_epb - 1) / (uint64_t)h->relay_epb);
-        if (h->relay && relay_alloc(h) != PMENV_OK) return fail(PMENV_ERR_HIP);
-    }
+    if (h->relay && relay_alloc(h) != PMENV_OK) return fail(PMENV_ERR_HIP);
     (void)flat1_invalidate(h, nullptr, kInvalSnap | kInvalHalo, true);   // no device sequencing yet
     char* base = (char*)h->state;
     h->value = (double*)(base + off[0]);
@@ -703,22 +383,16 @@ int pmenv_set_step_path(pmenv* h, int32_t path) {
         set_err(h, "unknown step path %d", path);
         return PMENV_ERR_ARG;
     }
-    const int bits = one_bits(h, path);
-    const int fbits = flat1_bits(h, path);
-    const int rbits = relay_bits(h, path);
-    if (bits < 0 || fbits < 0 || rbits < 0) {
+    StepPlan sel = *h;                     // the handle stays unchanged unless everything succeeds
+    if (step_plan_select(&sel, path) != PMENV_OK) {
         set_err(h, "step path %d does not fit this shape (one launch: F = 5, W >= 2, N <= 64, window <= 64 KiB "
                    "of LDS; two launches: F = 5, 16-B granular env windows; flat: F = 5, W >= 2, N <= 64, "
                    "16-B granular env windows of >= 148 chunks, N > 64 up to 512 with W >= 14; relay: F = 5, "
                    "W >= 2, 16-B granular env windows, N <= 512)", path);
         return PMENV_ERR_ARG;
     }
-    if (rbits && relay_alloc(h) != PMENV_OK) return PMENV_ERR_HIP;
-    h->path = path;
-    h->one = bits;
-    h->flat1 = fbits;
-    h->relay = rbits;
-    h->gen = gen_bits(h, path);
+    if (sel.relay && relay_alloc(h) != PMENV_OK) return PMENV_ERR_HIP;
+    static_cast<StepPlan&>(*h) = sel;
     return PMENV_OK;
 }
 
@@ -796,9 +470,15 @@ int pmenv_step_ex(pmenv* h, const pmenv_step_args* a, hipStream_t stream) {
     const int B = h->cfg.num_envs;
     const bool obs16 = (((uintptr_t)a->obs | (uintptr_t)p.obs_out) & 15u) == 0;
     const int fuse_bit = p.obs_out == p.obs ? PMENV_FUSE_INPLACE : PMENV_FUSE_DB;
-    if (a->bar && h->streaming && obs16 && (h->flat1 & fuse_bit)) {
+    // surface steps touch obs alone
+    const bool win16 = a->bar ? obs16 : (((uintptr_t)a->obs) & 15u) == 0;
+    const uint32_t ph = a->phases ? a->phases : (PMENV_PHASE_SCALAR | PMENV_PHASE_ADVANCE);
+    const StepRoute route = step_route(*h, !a->bar, fuse_bit, win16);
+    if (route != kRouteFlat1 && route != kRouteRelay)
+        if (const int rc = flat1_invalidate(h, stream)) return rc;   // every other path skips the snapshot
+    switch (route) {
+    case kRouteFlat1:
         // one launch over the flat stream: the whole step runs in the scalar phase
-        const uint32_t ph = a->phases ? a->phases : (PMENV_PHASE_SCALAR | PMENV_PHASE_ADVANCE);
         if (!(ph & PMENV_PHASE_SCALAR)) return PMENV_OK;
         // a step captured into a hipGraph replays with frozen arguments: from then on this
         // handle sequences its flat steps on the device (flat_seq_kernel + the kernel)
@@ -808,10 +488,8 @@ int pmenv_step_ex(pmenv* h, const pmenv_step_args* a, hipStream_t stream) {
         if (const int rc = relay_invalidate(h, stream, kInvalSnap | kInvalHalo)) return rc;
         launch_flat1(h, p, stream);
         return check_launch(h, "step_flat_kernel");
-    }
-    if (a->bar && h->streaming && obs16 && (h->relay & fuse_bit)) {
+    case kRouteRelay:
         // one launch, the scalar work relaying to the stream tiles (captured: device-sequenced)
-        const uint32_t ph = a->phases ? a->phases : (PMENV_PHASE_SCALAR | PMENV_PHASE_ADVANCE);
         if (!(ph & PMENV_PHASE_SCALAR)) return PMENV_OK;
         if (const int rc = flat1_invalidate(h, stream, kInvalSnap | kInvalHalo, false, true)) return rc;
         if (launch_relay(h, p, stream) != PMENV_OK) {
@@ -819,11 +497,8 @@ int pmenv_step_ex(pmenv* h, const pmenv_step_args* a, hipStream_t stream) {
             return PMENV_ERR_HIP;
         }
         return check_launch(h, "step_relay_kernel");
-    }
-    if (const int rc = flat1_invalidate(h, stream)) return rc;   // every other path skips the snapshot
-    if (!a->bar && h->surf_stream && (((uintptr_t)a->obs) & 15u) == 0) {
+    case kRouteSurfaceStream:
         // past the Infinity Cache: the scalar step, then the surface stream
-        const uint32_t ph = a->phases ? a->phases : (PMENV_PHASE_SCALAR | PMENV_PHASE_ADVANCE);
         if (ph & PMENV_PHASE_SCALAR) {
             launch_scalar_kernels(h, p, stream);
             if (const int rc = check_launch(h, "scalar_step_kernel")) return rc;
@@ -833,19 +508,15 @@ int pmenv_step_ex(pmenv* h, const pmenv_step_args* a, hipStream_t stream) {
             return check_launch(h, "surface_stream_kernel");
         }
         return PMENV_OK;
-    }
-    if (!a->bar) {
+    case kRouteSurface:
         if (a->phases == PMENV_PHASE_ADVANCE) return PMENV_OK;   // single launch: done in the scalar phase
         step_surface_kernel<<<B, kBlock, h->lds_surface, stream>>>(p);
         return check_launch(h, "step_surface_kernel");
-    }
-    if (h->streaming && obs16) {
-        const uint32_t ph = a->phases ? a->phases : (PMENV_PHASE_SCALAR | PMENV_PHASE_ADVANCE);
-        if (h->one & fuse_bit) {       // one launch: the whole step runs in the scalar phase
-            if (!(ph & PMENV_PHASE_SCALAR)) return PMENV_OK;
-            launch_one(h, p, stream);
-            return check_launch(h, "step_env_kernel");
-        }
+    case kRouteOne:                    // one launch: the whole step runs in the scalar phase
+        if (!(ph & PMENV_PHASE_SCALAR)) return PMENV_OK;
+        launch_one(h, p, stream);
+        return check_launch(h, "step_env_kernel");
+    case kRouteTwoLaunch:
         if (pmenv_tools::launch_fused(h, p, fuse_bit, ph, stream)) return check_launch(h, "tools: fused step");
         if (ph & PMENV_PHASE_SCALAR) {
             launch_scalar(h, p, stream);
@@ -857,10 +528,8 @@ int pmenv_step_ex(pmenv* h, const pmenv_step_args* a, hipStream_t stream) {
             return check_launch(h, "advance kernel");
         }
         return PMENV_OK;
-    }
-    if (h->gen_ok && (h->gen & fuse_bit) && obs16) {
+    case kRouteGen:
         // F != 5: the scalar step (copying the in-place stream's halo), then the generic stream
-        const uint32_t ph = a->phases ? a->phases : (PMENV_PHASE_SCALAR | PMENV_PHASE_ADVANCE);
         if (ph & PMENV_PHASE_SCALAR) {
             launch_scalar(h, p, stream);
             const int rc = check_launch(h, "scalar_step_kernel");
@@ -871,12 +540,14 @@ int pmenv_step_ex(pmenv* h, const pmenv_step_args* a, hipStream_t stream) {
             return check_launch(h, "advance_gen_kernel");
         }
         return PMENV_OK;
-    }
-    if (a->phases == PMENV_PHASE_ADVANCE) return PMENV_OK;   // single-launch path: all done in the scalar phase
-    if (h->small_block) {
+    case kRouteSmall:
+        if (a->phases == PMENV_PHASE_ADVANCE) return PMENV_OK;   // single-launch path: all done in the scalar phase
         launch_small(h, p, stream);
         return check_launch(h, h->tiny ? "step_tiny_kernel" : "step_small_kernel");
+    case kRouteLds:
+        break;
     }
+    if (a->phases == PMENV_PHASE_ADVANCE) return PMENV_OK;       // single-launch path, likewise
     if (h->vec && obs16)
         step_advance_lds_kernel<true><<<B, kBlock, h->lds_tile, stream>>>(p);
     else
@@ -1145,36 +816,16 @@ size_t pmenv_state_bytes(const pmenv* h) { return h ? h->state_bytes : 0; }
 
 const char* pmenv_step_path(const pmenv* h) {
     if (!h) return "";
-    // per window mode: the one-launch kernel, or the scalar step (K1) then the stream
-    const char* k1 = h->k1_vec ? "scalar_step_vec_kernel"
-                   : h->cfg.num_assets <= 64 ? "scalar_step_reg_kernel" : "scalar_step_kernel";
-    if (!h->streaming) {
-        const char* one = h->tiny ? "step_tiny_kernel" : h->small_block ? "step_small_kernel" : "step_advance_lds_kernel";
-        if (!h->gen) return one;
-        static thread_local char gout[320];
-        char g2[96];
-        snprintf(g2, sizeof g2, "%s+advance_gen_kernel", k1);
-        snprintf(gout, sizeof gout, "%s (obs_out) | %s (in place)", (h->gen & PMENV_FUSE_DB) ? g2 : one,
-                 (h->gen & PMENV_FUSE_INPLACE) ? g2 : one);
-        return gout;
-    }
-    const char* db2 = h->flat ? "advance_flat_wg_kernel" : "advance_rows_kernel";
-    const char* ip2 = h->flat_inplace ? "advance_flat_inplace_kernel" : "advance_rows_kernel";
-    static thread_local char buf[2][128], out[320];
-    const char* part[2];
-    for (int m = 0; m < 2; ++m) {          // 0 = double-buffered (obs_out), 1 = in place
-        const int bit = m ? PMENV_FUSE_INPLACE : PMENV_FUSE_DB;
-        if (h->relay & bit) part[m] = "step_relay_kernel";
-        else if (h->flat1 & bit) part[m] = h->cfg.num_assets > 64 ? "step_flat_vec_kernel" : "step_flat_kernel";
-        else if (h->one & bit) part[m] = "step_env_kernel";
-        else {
-            snprintf(buf[m], sizeof buf[m], "%s+%s", k1, m ? ip2 : db2);
-            part[m] = buf[m];
-        }
-    }
-    snprintf(out, sizeof out, "%s (obs_out) | %s (in place)%s%s", part[0], part[1],
-             h->device_seq && h->flat1 ? " [flat steps device-sequenced]" : "",
-             h->relay_dseq && h->relay ? " [relay steps device-sequenced]" : "");
+    static thread_local char out[512];
+    step_plan_describe(*h, h->cfg, (h->device_seq ? kDescribeFlatSeq : 0) | (h->relay_dseq ? kDescribeRelaySeq : 0),
+                       out, sizeof out);
+    return out;
+}
+
+const char* pmenv_step_path_for(const pmenv_cfg* cfg, int32_t path, int32_t detail) {
+    static thread_local char out[512];
+    out[0] = 0;
+    if (cfg) step_plan_path_for(*cfg, path, detail != 0, out, sizeof out);
     return out;
 }
 

@@ -67,6 +67,25 @@ def _version(t):
         return None
 
 
+def step_path_for(config=None, step_impl="auto", detail=False, **kw):
+    """pmenv_step_path_for: the kernels a step of this shape launches, as `TradingEnv.step_path`
+    reports them for a fresh env built with `step_impl`, worked out on the host alone (no
+    device, no handle). config: an EnvConfig, or give the constructor's keywords (num_envs,
+    num_assets, window, features and EnvConfig's fields; a close channel not given is
+    TradingEnv's). detail=True appends the plan's geometry (include/pmenv.h lists the fields).
+    "" where the library refuses the shape or the shape does not fit step_impl."""
+    if step_impl not in _abi.STEP_PATHS:
+        raise ValueError(f"step_impl must be one of {sorted(_abi.STEP_PATHS)}")
+    if config is None:
+        kw = dict(kw)
+        kw.setdefault("close_channel", min(3, kw.get("features", 5) - 2))
+        config = EnvConfig(**kw)
+    elif kw:
+        raise ValueError("give an EnvConfig or keywords, not both")
+    c = config.to_c()
+    return _abi.load().pmenv_step_path_for(ctypes.byref(c), _abi.STEP_PATHS[step_impl], int(bool(detail))).decode()
+
+
 class RingView:
     """Read-only view of the device weight ring with ActionBuffer's accessors
     (env/sim/weight_buffer.py:28-44); for inspection and tests, not the hot path."""

@@ -151,11 +151,11 @@ def test_c_caller_links_the_abi():
 
 
 def test_product_dispatch_has_no_conditional_compilation():
-    """The product's host side (pmenv.hip, launch.h, handle.h, replay_plan.h) reads straight through: no
+    """The product's host side (pmenv.hip, launch.h, handle.h, step_plan.h, replay_plan.h) reads straight through: no
     #if / #ifdef, no environment variable; the tools build's variants sit in tools/ab/
     behind the pmenv_tools hooks, whose product definitions are weak no-ops."""
     csrc = os.path.join(ROOT, "pm-rl_amd", "csrc")
-    for f in ("pmenv.hip", "launch.h", "handle.h", "replay_plan.h"):
+    for f in ("pmenv.hip", "launch.h", "handle.h", "step_plan.h", "replay_plan.h"):
         txt = open(os.path.join(csrc, f)).read()
         assert not re.search(r"^\s*#\s*if", txt, re.M), f"{f} has conditional compilation"
         assert "getenv" not in txt, f"{f} reads the environment"

@@ -431,7 +431,7 @@ void plan(pmenv* h) {
     t->one_v = knob_int("PMENV_ONE_V", kOneV);
     if (t->one_v != 1 && t->one_v != 2 && t->one_v != 3 && t->one_v != 6 && t->one_v != 8) t->one_v = kOneV;
     if (t->one_v != kOneV) {
-        plan_one(h, t->one_v);
+        plan_one(c, *h, t->one_v);
         h->one_auto = (h->one_ok && (win <= (48ll << 20) || !h->flat_inplace) ? (PMENV_FUSE_DB | PMENV_FUSE_INPLACE)
                                                                               : 0) & ~h->flat1_auto;
     }
@@ -467,7 +467,7 @@ void plan(pmenv* h) {
                                 (key == 51202 || key == 51204 || key == 102402 || key == 25604 || key == 25608 ||
                                  key == 25602 || key == 12808 || key == 12804);
             const bool wide = c.num_assets > 64 && (key == 25604 || key == 12808);
-            if ((narrow || wide) && flat1_fits(h, bk, vv)) {
+            if ((narrow || wide) && flat1_fits(c, *h, bk, vv)) {
                 h->flat1_block = bk;
                 h->flat1_vec = vv;
                 h->flat1_ok = true;
