@@ -46,7 +46,8 @@ extern "C" {
  *    replay of envs that end their episodes on their own, likewise; pmenv_rollout_gather_env and
  *    pmenv_rollout_gather_env_path, the compact rollout of such envs, likewise;
  *    pmenv_metrics_episodes, the trajectory metrics of such envs per episode, likewise;
- *    pmenv_step_path_for, the step's kernels and geometry for a cfg without a device, likewise) */
+ *    pmenv_step_path_for, the step's kernels and geometry for a cfg without a device, likewise;
+ *    pmenv_batch_reward_path, the batched reward's kernels by name, likewise) */
 #define PMENV_ABI_VERSION 4
 
 /* Opaque HIP stream (identical to HIP's own typedef); NULL = default stream. */
@@ -429,7 +430,9 @@ typedef enum pmenv_batch_norm {
 size_t pmenv_batch_reward_workspace(int32_t B);
 /* a, p [B, N]; v_prev [B] (the _v of pg.py); reward_kind LOG_RETURN / RETURN / SHARPE
  * (batch mean / std, pg.py:80); writes reward_out[0] (device) and optionally the
- * per-row gross returns ret_out [B]. */
+ * per-row gross returns ret_out [B]. a, p and grad_a need 4-B alignment only, work 8-B.
+ * Limit: B * N * 4 < 2^32 (the kernels address a, p and grad_a through 32-bit byte
+ * offsets; a larger batch is the caller's to split). */
 int pmenv_batch_reward_forward(const float* a, const float* v_prev, const float* p, int32_t B, int32_t N,
                                int32_t reward_kind, int32_t norm, double scale, double* work,
                                float* reward_out, float* ret_out, hipStream_t stream);
@@ -437,6 +440,17 @@ int pmenv_batch_reward_forward(const float* a, const float* v_prev, const float*
 int pmenv_batch_reward_backward(const float* a, const float* v_prev, const float* p, int32_t B, int32_t N,
                                 int32_t reward_kind, double scale, const double* work,
                                 const float* grad_out, float* grad_a, hipStream_t stream);
+/* The kernels a [B, N] batch takes, as a string of three fields joined by " | ": the
+ * forward's row kernel with its template argument (elements per lane; 0: the looping form),
+ * the backward kernel, and "parts=K", the number of partial records the forward's fold reads:
+ *   "batch_reward_small_kernel<8> | batch_reward_grad_quad_kernel<8> | parts=1"       (64 x 30)
+ *   "batch_reward_rows_quad_kernel<16> | batch_reward_grad_quad_kernel<16> | parts=2" (65 x 33)
+ *   "batch_reward_rows_kernel<0> | batch_reward_grad_kernel<0> | parts=1"             (3 x 700)
+ * (the small kernel folds its one record in the same launch; the others are followed by
+ * batch_reward_final_kernel and, with ret_out, batch_reward_select_kernel). "" for B < 1 or
+ * N < 1. The entry points above dispatch on the same decision. Host only: launches nothing,
+ * touches no device; the string is thread-local and valid until the thread's next call. */
+const char* pmenv_batch_reward_path(int32_t B, int32_t N);
 
 /* ---- device replay and trajectory metrics ---- */
 

@@ -1431,6 +1431,37 @@ int pmenv_metrics_episodes(const double* returns, const double* values, const fl
 
 size_t pmenv_batch_reward_workspace(int32_t B) { return B < 1 ? 0 : batch_reward_work_doubles(B) * 8; }
 
+// The batched reward's kernel choice for a [B, N] batch: the one decision the forward, the
+// backward and pmenv_batch_reward_path all read.
+//   N <= 64: a quad of lanes per row, EPL 8 (N <= 32) or 16 elements per lane, 64 rows per partial
+//            record; at most 64 rows (the agents' BATCH_SIZE, config/pg.py:7): the whole forward
+//            in one workgroup, one launch
+//   N  > 64: a wave per row, EPL 2 / 4 / 8 elements per lane in registers up to N = 512, EPL 0
+//            looping beyond; 16 rows per partial record
+struct BatchRewardPlan {
+    bool quad, small;
+    int epl, parts;
+};
+static BatchRewardPlan batch_reward_plan(int32_t B, int32_t N) {
+    BatchRewardPlan pl;
+    pl.quad = N <= kQuadMaxN;
+    pl.small = pl.quad && B <= kQuadRows;
+    pl.epl = N <= 32 ? 8 : N <= kQuadMaxN ? 16 : N <= 128 ? 2 : N <= 256 ? 4 : N <= 512 ? 8 : 0;
+    pl.parts = pl.quad ? (B + kQuadRows - 1) / kQuadRows : (int)batch_reward_blocks(B);
+    return pl;
+}
+
+const char* pmenv_batch_reward_path(int32_t B, int32_t N) {
+    thread_local char text[160];
+    text[0] = 0;
+    if (B < 1 || N < 1) return text;
+    const BatchRewardPlan pl = batch_reward_plan(B, N);
+    snprintf(text, sizeof(text), "%s<%d> | %s<%d> | parts=%d",
+             pl.small ? "batch_reward_small_kernel" : pl.quad ? "batch_reward_rows_quad_kernel" : "batch_reward_rows_kernel",
+             pl.epl, pl.quad ? "batch_reward_grad_quad_kernel" : "batch_reward_grad_kernel", pl.epl, pl.parts);
+    return text;
+}
+
 int pmenv_batch_reward_forward(const float* a, const float* v_prev, const float* p, int32_t B, int32_t N,
                                int32_t reward_kind, int32_t norm, double scale, double* work,
                                float* reward_out, float* ret_out, hipStream_t stream) {
@@ -1443,9 +1474,10 @@ int pmenv_batch_reward_forward(const float* a, const float* v_prev, const float*
     if (pmenv_tools::batch_reward_forward(a, v_prev, p, B, N, reward_kind, norm, scale, work, reward_out, ret_out,
                                           stream, &rc))
         return rc;
+    const BatchRewardPlan pl = batch_reward_plan(B, N);
     // at most 64 rows (the agents' BATCH_SIZE, config/pg.py:7): one workgroup, one launch
-    if (B <= kQuadRows && N <= kQuadMaxN) {
-        if (N <= 32)
+    if (pl.small) {
+        if (pl.epl == 8)
             batch_reward_small_kernel<8><<<1, kTrainBlock, 0, stream>>>(a, v_prev, p, B, N, reward_kind, norm, scale,
                                                                          work, reward_out, ret_out);
         else
@@ -1455,22 +1487,20 @@ int pmenv_batch_reward_forward(const float* a, const float* v_prev, const float*
     }
     // two launches: the row blocks' partials, then the final fold (a one-launch form with a
     // last-block ticket measured slower at every shape: DESIGN.md §7 f2)
-    int nparts;
-    if (N <= kQuadMaxN) {         // a quad of lanes per row
-        nparts = (B + kQuadRows - 1) / kQuadRows;
-        if (N <= 32)
-            batch_reward_rows_quad_kernel<8><<<(unsigned)nparts, kTrainBlock, 0, stream>>>(a, v_prev, p, B, N,
-                                                                                           reward_kind, norm, work);
+    const int nparts = pl.parts;
+    const unsigned g = (unsigned)nparts;
+    if (pl.quad) {                // a quad of lanes per row
+        if (pl.epl == 8)
+            batch_reward_rows_quad_kernel<8><<<g, kTrainBlock, 0, stream>>>(a, v_prev, p, B, N, reward_kind, norm, work);
         else
-            batch_reward_rows_quad_kernel<16><<<(unsigned)nparts, kTrainBlock, 0, stream>>>(a, v_prev, p, B, N,
-                                                                                            reward_kind, norm, work);
+            batch_reward_rows_quad_kernel<16><<<g, kTrainBlock, 0, stream>>>(a, v_prev, p, B, N, reward_kind, norm, work);
     } else {                      // wave per row, registers up to N = 512
-        nparts = (int)batch_reward_blocks(B);
-        const unsigned g = (unsigned)nparts;
-        if (N <= 128) batch_reward_rows_kernel<2><<<g, kTrainBlock, 0, stream>>>(a, v_prev, p, B, N, reward_kind, norm, work);
-        else if (N <= 256) batch_reward_rows_kernel<4><<<g, kTrainBlock, 0, stream>>>(a, v_prev, p, B, N, reward_kind, norm, work);
-        else if (N <= 512) batch_reward_rows_kernel<8><<<g, kTrainBlock, 0, stream>>>(a, v_prev, p, B, N, reward_kind, norm, work);
-        else batch_reward_rows_kernel<0><<<g, kTrainBlock, 0, stream>>>(a, v_prev, p, B, N, reward_kind, norm, work);
+        switch (pl.epl) {
+        case 2: batch_reward_rows_kernel<2><<<g, kTrainBlock, 0, stream>>>(a, v_prev, p, B, N, reward_kind, norm, work); break;
+        case 4: batch_reward_rows_kernel<4><<<g, kTrainBlock, 0, stream>>>(a, v_prev, p, B, N, reward_kind, norm, work); break;
+        case 8: batch_reward_rows_kernel<8><<<g, kTrainBlock, 0, stream>>>(a, v_prev, p, B, N, reward_kind, norm, work); break;
+        default: batch_reward_rows_kernel<0><<<g, kTrainBlock, 0, stream>>>(a, v_prev, p, B, N, reward_kind, norm, work);
+        }
     }
     batch_reward_final_kernel<<<1, kTrainBlock, 0, stream>>>(B, reward_kind, norm, scale, work, reward_out, nparts);
     // the chosen per-row return, when asked for (the backward takes each row's choice itself)
@@ -1482,25 +1512,27 @@ int pmenv_batch_reward_backward(const float* a, const float* v_prev, const float
                                 int32_t reward_kind, double scale, const double* work, const float* grad_out,
                                 float* grad_a, hipStream_t stream) {
     if (!a || !v_prev || !p || !work || !grad_out || !grad_a || B < 1 || N < 1) return PMENV_ERR_ARG;
-    const unsigned qgrid = (unsigned)((B + kQuadRows - 1) / kQuadRows);
-    if (N <= 32)
-        batch_reward_grad_quad_kernel<8><<<qgrid, kTrainBlock, 0, stream>>>(a, v_prev, p, B, N, reward_kind, scale,
-                                                                           work, grad_out, grad_a);
-    else if (N <= kQuadMaxN)
-        batch_reward_grad_quad_kernel<16><<<qgrid, kTrainBlock, 0, stream>>>(a, v_prev, p, B, N, reward_kind, scale,
-                                                                            work, grad_out, grad_a);
-    else if (N <= 128)
-        batch_reward_grad_kernel<2><<<(B + 3) / 4, 256, 0, stream>>>(a, v_prev, p, B, N, reward_kind, scale, work,
-                                                                     grad_out, grad_a);
-    else if (N <= 256)
-        batch_reward_grad_kernel<4><<<(B + 3) / 4, 256, 0, stream>>>(a, v_prev, p, B, N, reward_kind, scale, work,
-                                                                     grad_out, grad_a);
-    else if (N <= 512)
-        batch_reward_grad_kernel<8><<<(B + 3) / 4, 256, 0, stream>>>(a, v_prev, p, B, N, reward_kind, scale, work,
-                                                                     grad_out, grad_a);
-    else
-        batch_reward_grad_kernel<0><<<(B + 3) / 4, 256, 0, stream>>>(a, v_prev, p, B, N, reward_kind, scale, work,
-                                                                     grad_out, grad_a);
+    const BatchRewardPlan pl = batch_reward_plan(B, N);
+    const unsigned qgrid = (unsigned)pl.parts, wgrid = (unsigned)((B + 3) / 4);   // 64 rows | 4 rows per block
+    if (pl.quad) {
+        if (pl.epl == 8)
+            batch_reward_grad_quad_kernel<8><<<qgrid, kTrainBlock, 0, stream>>>(a, v_prev, p, B, N, reward_kind, scale,
+                                                                               work, grad_out, grad_a);
+        else
+            batch_reward_grad_quad_kernel<16><<<qgrid, kTrainBlock, 0, stream>>>(a, v_prev, p, B, N, reward_kind, scale,
+                                                                                work, grad_out, grad_a);
+    } else {
+        switch (pl.epl) {
+        case 2: batch_reward_grad_kernel<2><<<wgrid, 256, 0, stream>>>(a, v_prev, p, B, N, reward_kind, scale, work,
+                                                                       grad_out, grad_a); break;
+        case 4: batch_reward_grad_kernel<4><<<wgrid, 256, 0, stream>>>(a, v_prev, p, B, N, reward_kind, scale, work,
+                                                                       grad_out, grad_a); break;
+        case 8: batch_reward_grad_kernel<8><<<wgrid, 256, 0, stream>>>(a, v_prev, p, B, N, reward_kind, scale, work,
+                                                                       grad_out, grad_a); break;
+        default: batch_reward_grad_kernel<0><<<wgrid, 256, 0, stream>>>(a, v_prev, p, B, N, reward_kind, scale, work,
+                                                                        grad_out, grad_a);
+        }
+    }
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
 

@@ -409,8 +409,11 @@ __global__ __launch_bounds__(kTrainBlock) void batch_reward_grad_quad_kernel(con
         z = quad_sum(z);
         const double rz = 1.0 / z;
         double wg = 0.0;                                          // sum_m w_m g_m
+        // past the row q.p[i] is the next rows' p (the 16-B loads run on): e[i] = 0 there, but
+        // 0 * inf = NaN, so the term is skipped as in the forward (for finite p it is +-0)
 #pragma unroll
-        for (int i = 0; i < EPL; ++i) wg += (e[i] * rz) * (dr * (v * (double)q.p[i]) / v);
+        for (int i = 0; i < EPL; ++i)
+            if (g * EPL + i < N) wg += (e[i] * rz) * (dr * (v * (double)q.p[i]) / v);
         wg = quad_sum(wg);
 #pragma unroll
         for (int i = 0; i < EPL; ++i) out[i] = (float)((e[i] * rz) * (dr * (v * (double)q.p[i]) / v - wg));

@@ -20,7 +20,8 @@ PMENV_ABI_VERSION = 4   # 2: pmenv_window_written / pmenv_state_written; cfg def
                         #    pmenv_replay_path added under 4: load() names a missing symbol;
                         #    pmenv_replay_valid_build / _select, pmenv_replay_gather_nstep_env /
                         #    _seq_env and pmenv_prio_fill_env likewise; pmenv_rollout_gather_env and
-                        #    pmenv_rollout_gather_env_path likewise; pmenv_step_path_for likewise)
+                        #    pmenv_rollout_gather_env_path likewise; pmenv_step_path_for and
+                        #    pmenv_batch_reward_path likewise)
 
 # enums (include/pmenv.h)
 REWARD_KINDS = {"log_returns": 0, "returns": 1, "sharpe_ratio": 2, "diff_sharpe": 3}
@@ -135,6 +136,7 @@ SIGNATURES = [
      [_P, _P, _P, _I32, _I32, _I32, _I32, ctypes.c_double, _P, _P, _P, _P]),
     ("pmenv_batch_reward_backward", ctypes.c_int,
      [_P, _P, _P, _I32, _I32, _I32, ctypes.c_double, _P, _P, _P, _P]),
+    ("pmenv_batch_reward_path", ctypes.c_char_p, [_I32, _I32]),
 ]
 
 _lib = None
