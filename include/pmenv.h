@@ -47,7 +47,9 @@ extern "C" {
  *    pmenv_rollout_gather_env_path, the compact rollout of such envs, likewise;
  *    pmenv_metrics_episodes, the trajectory metrics of such envs per episode, likewise;
  *    pmenv_step_path_for, the step's kernels and geometry for a cfg without a device, likewise;
- *    pmenv_batch_reward_path, the batched reward's kernels by name, likewise) */
+ *    pmenv_batch_reward_path, the batched reward's kernels by name, likewise;
+ *    pmenv_ffd_weights, pmenv_ffd_apply, pmenv_ffd_path, pmenv_scale_workspace, pmenv_scale_fit
+ *    and pmenv_scale_apply, the loader's feature stages on the device, likewise) */
 #define PMENV_ABI_VERSION 4
 
 /* Opaque HIP stream (identical to HIP's own typedef); NULL = default stream. */
@@ -415,6 +417,58 @@ const char* pmenv_gae_path(int32_t T, int32_t B, size_t work_bytes, int work_ali
  * partials; two calls in flight need two workspaces). Deterministic. */
 size_t pmenv_moments_workspace(void);
 int pmenv_moments(const float* x, int64_t n, double* out, double* work, hipStream_t stream);
+
+/* ---- the loader's feature stages on the device (data/ffd.py, data/instrument.py:257-336):
+ * fixed-width-window fractional differencing and the per-column scalers over x [T, C] f32,
+ * the C = N * (F-1) columns contiguous (the [T, N, F-1] bar layout). ---- */
+
+/* data/ffd.py:38-47 as the reference's CPU path computes it: the taps of order d over a
+ * series of T rows, w_0 = 1, w_k = f32(prod_{i <= k} p_i), p_k = (-(d+1)) / k + 1 in f32, the
+ * running product in f64 and every tap rounded to f32; *width = max{k < T : |w_k| > thres}
+ * (:43) and the filter is taps 0 .. width-1 (:47 drops tap `width` itself: d = 1 gives the
+ * single tap [1], the identity). d = 0: "leave the column alone", width 0 (:84). Writes
+ * min(*width, cap) taps; taps may be NULL with cap = 0 (the width only). Host only.
+ * PMENV_ERR_ARG: T < 2, d or thres negative or not finite, NULL width. */
+int pmenv_ffd_weights(double d, double thres, int32_t T, float* taps, int32_t cap, int32_t* width);
+/* data/ffd.py:80-89 (one conv1d per column, clipped by the widest filter) in one launch:
+ * out[r, c] = sum_{j < width[c]} taps[j, c] * x[max_width + r - j, c] for r < T - max_width.
+ * taps [max_width, C] f32 (tap-major; rows >= width[c] of a column are not read), width [C]
+ * int32 on the device (clamped to [0, max_width]), out [T - max_width, C] f32. Each output is
+ * one f64 chain in ascending j, acc = fma((double)w_j, (double)x[t-j], acc) from 0, rounded
+ * once to f32: the product of two f32 values is exact in f64, so the bits depend on no
+ * geometry. A column of width 0 copies x[max_width + r]. A NaN in x makes exactly the
+ * width[c] outputs of its column that read it NaN. out must overlap neither x nor taps
+ * (PMENV_ERR_ARG); max_width >= T, T < 1, C < 1: PMENV_ERR_ARG. 4-B alignment. No allocation,
+ * no synchronisation, capturable. */
+int pmenv_ffd_apply(const float* x, int32_t T, int32_t C, const float* taps, const int32_t* width,
+                    int32_t max_width, float* out, hipStream_t stream);
+/* The kernel pmenv_ffd_apply launches for a shape and its geometry, e.g.
+ *   "ffd_apply_kernel<8,8> cw=64 slots=1 rows=32 grid=345x4 block=256"
+ * <outputs per lane, taps per block>, cw columns and slots time slots per wave, rows output
+ * rows per workgroup, grid = time chunks x column groups. "" for a refused shape. Host only;
+ * the string is thread-local and valid until the thread's next call. */
+const char* pmenv_ffd_path(int32_t T, int32_t C, int32_t max_width);
+
+/* data/instrument.py:318-336 (sklearn's MinMaxScaler / StandardScaler fitted per (ticker,
+ * feature) column, config/base.py:25). */
+typedef enum pmenv_scale_method {
+    PMENV_SCALE_MINMAX = 0,   /* stats = {min, max};  y = (x - min) / (max - min) */
+    PMENV_SCALE_STANDARD = 1  /* stats = {mean, std} (ddof 0); y = (x - mean) / std */
+} pmenv_scale_method;
+/* Device scratch of a [T, C] fit in bytes (two doubles per 256-row chunk and column; two
+ * fits in flight need two workspaces). 0 for a refused shape. */
+size_t pmenv_scale_workspace(int32_t T, int32_t C);
+/* stats [2, C] f64 on the device from x [T, C]; NaNs are skipped as sklearn's nanmin /
+ * nanmax / nanmean do (a column without a number: NaN stats). The standard fit takes two
+ * passes in f64, the mean and then the squares about it. Deterministic; stats and work 8-B
+ * aligned. No allocation, no synchronisation, capturable. */
+int pmenv_scale_fit(const float* x, int32_t T, int32_t C, int32_t method, double* stats, double* work,
+                    size_t work_bytes, hipStream_t stream);
+/* y[t, c] = f32(((double)x[t, c] - stats[0, c]) / den), den = max - min or std, 1 where that
+ * is 0 (sklearn's zero-scale rule); a NaN passes through. stats may come from any fit (test
+ * rows scaled with train statistics); y may be x. */
+int pmenv_scale_apply(const float* x, int32_t T, int32_t C, int32_t method, const double* stats, float* y,
+                      hipStream_t stream);
 
 /* ---- trainer-side twin: the differentiable batched portfolio reward of the
  * PG / A2C agents (agent/pg/pg.py:40-82 `_reward`, agent/a2c.py/a2c.py:40-82 `_loss`

@@ -5,7 +5,8 @@
 // fallbacks), scalar_vec.h (packed scalar step), data.h (synthetic market data),
 // rollout.h (GAE, moments), replay.h (replay gather, metrics), metrics_env.h (the metrics
 // per episode) and trainer.h (batched reward); the step's launchers in launch.h, the
-// handle in handle.h, its shape plan — which kernel a step takes, in which geometry — in
+// handle in handle.h, features.h (fractional differencing, column scalers; their plan in
+// ffd_plan.h), its shape plan — which kernel a step takes, in which geometry — in
 // step_plan.h, the sample gathers' kernel choice in replay_plan.h (both host only).
 //
 // Every entry point enqueues on the caller's stream and never synchronises, allocates or
@@ -28,6 +29,8 @@
 #include "../../include/pmenv.h"
 #include "data.h"
 #include "episode.h"
+#include "features.h"
+#include "ffd_plan.h"
 #include "handle.h"
 #include "launch.h"
 #include "metrics_env.h"
@@ -1049,6 +1052,67 @@ int pmenv_moments(const float* x, int64_t n, double* out, double* work, hipStrea
     const int blocks = (int)(want < 1 ? 1 : (want > kMomBlocks ? kMomBlocks : want));
     moments_partial_kernel<<<blocks, kMomBlock, 0, stream>>>(x, n, work);
     moments_final_kernel<<<1, kMomBlock, 0, stream>>>(blocks, n, work, out);
+    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
+// ---- the feature pipeline: ffd_plan.h holds the weights and the geometry, features.h the kernels
+int pmenv_ffd_weights(double d, double thres, int32_t T, float* taps, int32_t cap, int32_t* width) {
+    return ffd_weights(d, thres, T, taps, cap, width);
+}
+
+const char* pmenv_ffd_path(int32_t T, int32_t C, int32_t max_width) {
+    thread_local char text[160];
+    ffd_plan_describe(ffd_plan(T, C, max_width), text, sizeof(text));
+    return text;
+}
+
+int pmenv_ffd_apply(const float* x, int32_t T, int32_t C, const float* taps, const int32_t* width, int32_t max_width,
+                    float* out, hipStream_t stream) {
+    if (!x || !width || !out || (max_width > 0 && !taps)) return PMENV_ERR_ARG;
+    if (((uintptr_t)x | (uintptr_t)taps | (uintptr_t)width | (uintptr_t)out) & 3u) return PMENV_ERR_ALIGN;
+    const FfdPlan plan = ffd_plan(T, C, max_width);
+    if (!plan.ok) return PMENV_ERR_ARG;
+    // out must overlap neither x nor the tap table: a lane reads rows other lanes write
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (size_t)(T - max_width) * (size_t)C * sizeof(float);
+    const uintptr_t x0 = (uintptr_t)x, x1 = x0 + (size_t)T * (size_t)C * sizeof(float);
+    const uintptr_t w0 = (uintptr_t)taps, w1 = w0 + (size_t)max_width * (size_t)C * sizeof(float);
+    if ((o0 < x1 && x0 < o1) || (max_width > 0 && o0 < w1 && w0 < o1)) return PMENV_ERR_ARG;
+    ffd_apply_kernel<kFfdRB, kFfdJB><<<dim3(plan.grid_x, plan.grid_y), plan.block, 0, stream>>>(
+        x, taps, width, out, T, C, max_width, plan.cw_log2);
+    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
+size_t pmenv_scale_workspace(int32_t T, int32_t C) { return scale_workspace(T, C); }
+
+int pmenv_scale_fit(const float* x, int32_t T, int32_t C, int32_t method, double* stats, double* work,
+                    size_t work_bytes, hipStream_t stream) {
+    const int64_t chunks = scale_chunks(T, C);
+    if (!x || !stats || !work || chunks < 1 || (method != PMENV_SCALE_MINMAX && method != PMENV_SCALE_STANDARD) ||
+        work_bytes < scale_workspace(T, C))
+        return PMENV_ERR_ARG;
+    if (((uintptr_t)x & 3u) || (((uintptr_t)stats | (uintptr_t)work) & 7u)) return PMENV_ERR_ALIGN;
+    const dim3 grid((unsigned)((C + 63) / 64), (unsigned)chunks);
+    const unsigned fin = (unsigned)((C + 255) / 256);
+    if (method == PMENV_SCALE_MINMAX) {
+        scale_partial_kernel<0><<<grid, 256, 0, stream>>>(x, T, C, stats, work);
+        scale_final_kernel<0><<<fin, 256, 0, stream>>>((int)chunks, C, work, stats);
+    } else {                                          // two passes: the mean, then the squares about it
+        scale_partial_kernel<1><<<grid, 256, 0, stream>>>(x, T, C, stats, work);
+        scale_final_kernel<1><<<fin, 256, 0, stream>>>((int)chunks, C, work, stats);
+        scale_partial_kernel<2><<<grid, 256, 0, stream>>>(x, T, C, stats, work);
+        scale_final_kernel<2><<<fin, 256, 0, stream>>>((int)chunks, C, work, stats);
+    }
+    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
+int pmenv_scale_apply(const float* x, int32_t T, int32_t C, int32_t method, const double* stats, float* y,
+                      hipStream_t stream) {
+    if (!x || !stats || !y || T < 1 || C < 1 || (method != PMENV_SCALE_MINMAX && method != PMENV_SCALE_STANDARD) ||
+        ((int64_t)C + 63) / 64 > 65535)
+        return PMENV_ERR_ARG;
+    if ((((uintptr_t)x | (uintptr_t)y) & 3u) || ((uintptr_t)stats & 7u)) return PMENV_ERR_ALIGN;
+    const dim3 grid((unsigned)(((int64_t)T + 31) / 32), (unsigned)((C + 63) / 64));
+    scale_apply_kernel<<<grid, 256, 0, stream>>>(x, T, C, method == PMENV_SCALE_STANDARD, stats, y);
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
 

@@ -21,7 +21,7 @@ PMENV_ABI_VERSION = 4   # 2: pmenv_window_written / pmenv_state_written; cfg def
                         #    pmenv_replay_valid_build / _select, pmenv_replay_gather_nstep_env /
                         #    _seq_env and pmenv_prio_fill_env likewise; pmenv_rollout_gather_env and
                         #    pmenv_rollout_gather_env_path likewise; pmenv_step_path_for and
-                        #    pmenv_batch_reward_path likewise)
+                        #    pmenv_batch_reward_path likewise; pmenv_ffd_* and pmenv_scale_* likewise)
 
 # enums (include/pmenv.h)
 REWARD_KINDS = {"log_returns": 0, "returns": 1, "sharpe_ratio": 2, "diff_sharpe": 3}
@@ -56,6 +56,7 @@ class PmenvStepArgs(ctypes.Structure):
 PHASE_SCALAR = 1
 PHASE_ADVANCE = 2
 STEP_PATHS = {"auto": 0, "one_launch": 1, "two_launch": 2, "flat": 3, "relay": 4}
+SCALE_METHODS = {"minmax": 0, "standard": 1}   # pmenv_scale_method
 REPLAY_KINDS = {"one_step": 0, "nstep": 1, "seq": 2, "rollout": 3}   # pmenv_replay_kind
 
 
@@ -137,6 +138,12 @@ SIGNATURES = [
     ("pmenv_batch_reward_backward", ctypes.c_int,
      [_P, _P, _P, _I32, _I32, _I32, ctypes.c_double, _P, _P, _P, _P]),
     ("pmenv_batch_reward_path", ctypes.c_char_p, [_I32, _I32]),
+    ("pmenv_ffd_weights", ctypes.c_int, [ctypes.c_double, ctypes.c_double, _I32, _P, _I32, ctypes.POINTER(_I32)]),
+    ("pmenv_ffd_apply", ctypes.c_int, [_P, _I32, _I32, _P, _P, _I32, _P, _P]),
+    ("pmenv_ffd_path", ctypes.c_char_p, [_I32, _I32, _I32]),
+    ("pmenv_scale_workspace", _SZ, [_I32, _I32]),
+    ("pmenv_scale_fit", ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P, _SZ, _P]),
+    ("pmenv_scale_apply", ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P, _P]),
 ]
 
 _lib = None

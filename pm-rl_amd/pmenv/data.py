@@ -17,14 +17,32 @@ from . import _abi
 
 
 class MarketSeries:
-    def __init__(self, bars, device=None):
-        """bars: [T, N, F-1] market channels (e.g. [open, high, low, close]) as numpy or torch."""
+    def __init__(self, bars, device=None, relatives=None):
+        """bars: [T, N, F-1] market channels (e.g. [open, high, low, close]) as numpy or torch.
+        relatives: [T, N] price relatives of its own, row t belonging to bars[t], for a series
+        whose close channel is no price any more (pmenv.features.build: differenced and scaled
+        channels); the step and the compact rollout buffer then take p from this table
+        instead of bars[t, :, close] / last close. None: raw bars, as before."""
         t = torch.as_tensor(np.asarray(bars) if not torch.is_tensor(bars) else bars)
         if t.dim() != 3:
             raise ValueError("bars must be [T, N, F-1]")
         self.bars = t.to(device=device or "cuda", dtype=torch.float32).contiguous()
         self.days, self.num_assets, self.channels = self.bars.shape
         self.device = self.bars.device
+        self.relatives = None
+        if relatives is not None:
+            r = torch.as_tensor(np.asarray(relatives) if not torch.is_tensor(relatives) else relatives)
+            if r.dim() != 2 or r.shape[0] != self.days or r.shape[1] != self.num_assets:
+                raise ValueError(f"relatives must be [{self.days}, {self.num_assets}]: one row per bar")
+            self.relatives = r.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def relatives_at(self, day):
+        """relatives[day] per env, [B, N]; NaN for a day outside [0, T), as the bar reads.
+        Index arithmetic on the device only: capturable."""
+        day = day.long()
+        ok = (day >= 0) & (day < self.days)
+        p = self.relatives[day.clamp(0, max(self.days - 1, 0))]
+        return torch.where(ok.unsqueeze(-1), p, torch.full_like(p, float("nan")))
 
     def initial_window(self, start, window):
         """obs [B, N, W, F] with obs[b, :, t, :F-1] = bars[start[b] + t]; channel F-1 = 0 (reset fills it)."""

@@ -26,7 +26,9 @@ Two storage forms for the observations s:
   = 126 GB of a 288 GB MI355X) — for bar feeds that are not a resident series.
 
 The price relatives p are not stored in either form: p[t] = close_t / close_{t-1} of
-the window's last day, the same fp32 quotient the env formed (instrument.py:79).
+the window's last day, the same fp32 quotient the env formed (instrument.py:79) — or, for a
+series that carries its own relatives (MarketSeries.relatives, pmenv.features.build: its
+close channel is a differenced, scaled value), the row of that table the step read.
 
 `returns(values, gamma, lam)` runs the GAE / discounted-return pass over the stored
 rewards on device (pmenv_gae_ex).
@@ -221,23 +223,32 @@ class DeviceRolloutBuffer:
                    None, "pmenv_rollout_gather")
         return out
 
+    def _last_day(self, t, env):
+        """series day of the last day of the windows after t steps (compact form), [S]."""
+        if self.episodes:
+            # the bar step t appended lies behind the window after t - 1 steps (the window
+            # after t steps may already be the restarted one); t = 0: the reset window's last
+            return torch.where(t > 0, self.first[(t - 1).clamp(min=0), env].long() + self.W,
+                               self.first[t, env].long() + self.W - 1)
+        return self.start[env].long() + t + self.W - 1
+
     def _close(self, t, env):
         """close of the last day of the windows after t steps, [S, N]."""
         if not self.compact:
             return self.s[t, env, :, self.W - 1, self.close_ch]
-        if self.episodes:
-            # the bar step t appended lies behind the window after t - 1 steps (the window
-            # after t steps may already be the restarted one); t = 0: the reset window's last
-            day = torch.where(t > 0, self.first[(t - 1).clamp(min=0), env].long() + self.W,
-                              self.first[t, env].long() + self.W - 1)
-        else:
-            day = self.start[env].long() + t + self.W - 1
-        return self.series.bars[day, :, self.close_ch]
+        return self.series.bars[self._last_day(t, env), :, self.close_ch]
+
+    def _table(self):
+        """the series' own relatives (pmenv.features.build), or None: p is a quotient of closes"""
+        return getattr(self.series, "relatives", None) if self.compact else None
 
     def price_relatives(self, t):
-        """p of step t (1 <= t < step): close_t / close_{t-1} of every asset, [B, N]."""
+        """p of step t (1 <= t < step), [B, N]: the row of the series' relatives table the
+        step read where the series carries one, else close_t / close_{t-1} of every asset."""
         env = torch.arange(self.B, device=self.device)
         tt = torch.full((self.B,), t, dtype=torch.long, device=self.device)
+        if self._table() is not None:
+            return self.series.relatives_at(self._last_day(tt, env))
         if self.episodes:
             day = self.first[t - 1].long() + self.W
             bars = self.series.bars
@@ -264,7 +275,10 @@ class DeviceRolloutBuffer:
             v_prev = torch.where(fresh, torch.full_like(v_prev, self.init_cash), v_prev)
         # :133 — only the last day's close of the next window is read (no [S, N, W, F]
         # copy of the next windows)
-        p = (self._close(t, env) / s[..., self.W - 1, self.close_ch]).reshape(S, self.N, 1)
+        if self._table() is not None:      # a series of features: the step took p from its table
+            p = self.series.relatives_at(self._last_day(t, env)).reshape(S, self.N, 1)
+        else:
+            p = (self._close(t, env) / s[..., self.W - 1, self.close_ch]).reshape(S, self.N, 1)
         return s, a, r, v_prev, a_prev, p
 
     def _pairs(self, order):

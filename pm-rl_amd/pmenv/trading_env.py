@@ -465,7 +465,8 @@ class TradingEnv:
                                  default to bar.close / window[W-1].close.
         series, day            : resident data path — `series` is a pmenv.data.MarketSeries
                                  (or a [T, N, F-1] tensor) and env b takes day[b]'s
-                                 bar from it (instead of `bar`)
+                                 bar from it (instead of `bar`); a series with a
+                                 relatives table supplies prices = relatives[day]
         out (fused path only)  : write the advanced window into `out` instead of
                                  in place (double-buffered windows, as the
                                  reference's data path hands the env a fresh
@@ -614,6 +615,10 @@ class TradingEnv:
                 raise ValueError("day must hold one index per env")
             br, days = sb, sb.shape[0]
             bar = sb
+            # a series that carries its own relatives (pmenv.features.build: its close channel
+            # is a differenced, scaled value): the step is given prices = relatives[day]
+            if p is None and getattr(series, "relatives", None) is not None:
+                p = series.relatives_at(dy).contiguous()
         elif bar is not None:
             br = self._vec(bar, N * (cfg.features - 1), "bar")
         elif p is None:
