@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from rollout_window_ref import window_ref
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 
@@ -65,44 +67,27 @@ def _assert_form(N, W, S, form):
     assert env_path.split(" ")[1:] == lock.split(" ")[1:]            # the same plan
 
 
-def gather_env(m, N, W, first, updates, weights, carry, T_rec, B, ring, ti, ei, out=None):
+def gather_env(m, N, W, first, updates, weights, carry, T_rec, B, ring, ti, ei, out=None, F=5):
+    """pmenv_rollout_gather_env through the raw ABI; m: anything with the series as .bars [Ts, N, F-1]
+    (a view too); out: the [S, N, W, F] floats to write (a view too), a fresh tensor if None."""
     from pmenv import _abi
     S = ti.numel()
     if out is None:
-        out = torch.empty(S, N, W, 5, device=DEV)
-    _abi.check(_abi.load().pmenv_rollout_gather_env(_p(m.bars), m.bars.shape[0], N, 5, W, _p(first), _p(updates),
+        out = torch.empty(S, N, W, F, device=DEV)
+    _abi.check(_abi.load().pmenv_rollout_gather_env(_p(m.bars), m.bars.shape[0], N, F, W, _p(first), _p(updates),
                                                     _p(weights), carry, T_rec, B, _abi.RING_MODES[ring], _p(ti),
                                                     _p(ei), S, _p(out), _stream()), None, "pmenv_rollout_gather_env")
     return out
 
 
-def gather_lockstep(m, N, W, start, weights, T_rec, B, ring, ti, ei):
+def gather_lockstep(m, N, W, start, weights, T_rec, B, ring, ti, ei, out=None, F=5):
+    """pmenv_rollout_gather through the raw ABI; m, out, F as gather_env's."""
     from pmenv import _abi
     S = ti.numel()
-    out = torch.empty(S, N, W, 5, device=DEV)
-    _abi.check(_abi.load().pmenv_rollout_gather(_p(m.bars), m.bars.shape[0], N, 5, W, _p(start), _p(weights), T_rec, B,
+    if out is None:
+        out = torch.empty(S, N, W, F, device=DEV)
+    _abi.check(_abi.load().pmenv_rollout_gather(_p(m.bars), m.bars.shape[0], N, F, W, _p(start), _p(weights), T_rec, B,
                                                 _abi.RING_MODES[ring], _p(ti), _p(ei), S, _p(out), _stream()))
-    return out
-
-
-def window_ref(bars, first, updates, weights, carry, W, ring, t, b):
-    """include/pmenv.h's data model for one window (t, b), [N, W, 5], in numpy."""
-    Ts, N, _ = bars.shape
-    out = np.empty((N, W, 5), np.float32)
-    d0, u = int(first[t, b]), int(updates[t, b])
-    for p in range(W):
-        d = d0 + p
-        out[:, p, :4] = bars[d] if 0 <= d < Ts else np.nan
-        c = (p - u - 1) % W if ring == "storage" and u >= W - 1 else p
-        r = u + c
-        if r < W - 1:
-            out[:, p, 4] = 0.0
-        elif r == W - 1:
-            out[:, p, 4] = 0.0
-            out[0, p, 4] = 1.0
-        else:
-            row = carry + t + c - W
-            out[:, p, 4] = weights[row, b] if 0 <= row < weights.shape[0] else 0.0
     return out
 
 
