@@ -49,7 +49,9 @@ extern "C" {
  *    pmenv_step_path_for, the step's kernels and geometry for a cfg without a device, likewise;
  *    pmenv_batch_reward_path, the batched reward's kernels by name, likewise;
  *    pmenv_ffd_weights, pmenv_ffd_apply, pmenv_ffd_path, pmenv_scale_workspace, pmenv_scale_fit
- *    and pmenv_scale_apply, the loader's feature stages on the device, likewise) */
+ *    and pmenv_scale_apply, the loader's feature stages on the device, likewise;
+ *    pmenv_ind_layout, pmenv_ind_workspace, pmenv_ind_apply and pmenv_ind_path, the loader's
+ *    technical indicators on the device, likewise) */
 #define PMENV_ABI_VERSION 4
 
 /* Opaque HIP stream (identical to HIP's own typedef); NULL = default stream. */
@@ -469,6 +471,68 @@ int pmenv_scale_fit(const float* x, int32_t T, int32_t C, int32_t method, double
  * rows scaled with train statistics); y may be x. */
 int pmenv_scale_apply(const float* x, int32_t T, int32_t C, int32_t method, const double* stats, float* y,
                       hipStream_t stream);
+
+/* ---- the loader's technical indicators on the device (data/instrument.py:207-232 runs TA-Lib
+ * once per ticker over the f64 OHLCV columns and appends every output as an f32 channel;
+ * config/base.py:30-44 names the eleven below). bars [T, N, C] f32; every element is widened
+ * to f64 on load, all arithmetic is f64, every output is rounded once to f32. The definitions
+ * are this header's (DESIGN.md "Technical indicators" has the table): TA-Lib's default
+ * algorithms restated — SMA-seeded EMA, Wilder smoothing, unstable period 0, SMA smoothing
+ * only — with one deliberate deviation: dx is 0 where its true-range sum or DI- + DI+ is
+ * within 1e-8 of zero (TA-Lib repeats its previous output). ---- */
+typedef enum pmenv_ind_kind {
+    PMENV_IND_EMA = 0,     /* p = {timeperiod};                       1 output,  L = p-1 */
+    PMENV_IND_BBANDS = 1,  /* p = {timeperiod}, f = {nbdevup, nbdevdn}; upper, middle, lower; L = p-1 */
+    PMENV_IND_MACD = 2,    /* p = {fast, slow, signal} (swapped if slow < fast); macd, signal, hist; L = slow-1 + signal-1 */
+    PMENV_IND_ATR = 3,     /* p = {timeperiod};                       L = p */
+    PMENV_IND_RSI = 4,     /* p = {timeperiod};                       L = p */
+    PMENV_IND_ADX = 5,     /* p = {timeperiod};                       L = 2p-1 */
+    PMENV_IND_DX = 6,      /* p = {timeperiod};                       L = p */
+    PMENV_IND_STOCH = 7,   /* p = {fastk, slowk, slowd};              slowk, slowd; L = the three periods - 3 */
+    PMENV_IND_CCI = 8,     /* p = {timeperiod};                       L = p-1 */
+    PMENV_IND_OBV = 9,     /* no parameter;                           L = 0 */
+    PMENV_IND_ADOSC = 10   /* p = {fast, slow};                       L = max(fast, slow) - 1 */
+} pmenv_ind_kind;
+typedef struct pmenv_ind_op {
+    int32_t kind;          /* pmenv_ind_kind */
+    int32_t p[3];          /* the periods, each 2 .. 256; unused entries are ignored */
+    double f[2];           /* bbands: the band multipliers */
+} pmenv_ind_op;
+/* *n_out = K, the output columns of the ops in order; *lookback = L, the largest lookback
+ * (either may be NULL). Host only. PMENV_ERR_ARG: NULL ops, n_ops outside 1 .. 32, an unknown
+ * kind, a period outside 2 .. 256, a band multiplier that is not finite. */
+int pmenv_ind_layout(const pmenv_ind_op* ops, int32_t n_ops, int32_t* n_out, int32_t* lookback);
+/* Device scratch of one call in bytes: the split form's segment records and stoch's fastk
+ * stream. May be 0 for a valid call; 0 for a refused shape too. */
+size_t pmenv_ind_workspace(int32_t T, int32_t N, const pmenv_ind_op* ops, int32_t n_ops);
+/* out[(r * N + n) * ldo + col0 + k] = output k of the call at series row L + r, for r < T - L,
+ * n < N, k < K: every op is aligned to the call's lookback, and nothing else of out is
+ * written (ldo > K leaves the other channels of a combined [T - L, N, ldo] tensor alone).
+ * chan[5] = the channels of open, high, low, close, volume in bars; -1 for one no op needs.
+ * Windowed values (sums, sums of squares, max, min, mean absolute deviation over the trailing
+ * p rows) are one ascending f64 chain per output and depend on no geometry; the recurrences
+ * (EMA, Wilder average and sum, running sum) run one lane per column over all rows
+ * (ind_scan_seq_kernel) or, for few columns, over row segments whose carries are composed in
+ * order (ind_scan_split_kernel) — pmenv_ind_path names the choice. The split form's carries
+ * differ from the sequential chain by ~1e-16 of a state's magnitude: outputs agree to the f32
+ * bit except where an output is the difference of two states that have converged on one value
+ * (adosc on a flat A/D line, macd on a constant close), which is rounding noise in either form.
+ * A NaN or inf follows IEEE
+ * through the definitions: it poisons the windowed outputs that read it and its column's
+ * recurrences from that row on, never another column. PMENV_ERR_ARG: what pmenv_ind_layout
+ * refuses, T <= L, N < 1, a needed channel that is -1 or >= C, col0 < 0 or col0 + K > ldo, out
+ * overlapping bars, and, when pmenv_ind_workspace is not 0, NULL work, work not 8-B aligned
+ * or work_bytes below it. PMENV_ERR_ALIGN: bars or out not 4-B aligned. The result does not depend on
+ * what work held. No allocation, no synchronisation, capturable. */
+int pmenv_ind_apply(const float* bars, int32_t T, int32_t N, int32_t C, const int32_t chan[5],
+                    const pmenv_ind_op* ops, int32_t n_ops, float* out, int32_t ldo, int32_t col0, void* work,
+                    size_t work_bytes, hipStream_t stream);
+/* The kernels of that call in launch order with their geometry, " | " between them, e.g.
+ *   "ind_scan_split_kernel walks=1 seg=78 segs=64 grid=8x64 block=64 | ind_fastk_kernel grid=9961 block=256 | ind_window_kernel ops=3 grid=9896 block=256"
+ * walks: launches of the recurrences (one op of each kind per walk); seg / segs: rows per
+ * segment and segments. "" for a refused shape. Host only; thread-local, valid until the
+ * thread's next call; read from the plan pmenv_ind_apply dispatches on. */
+const char* pmenv_ind_path(int32_t T, int32_t N, const pmenv_ind_op* ops, int32_t n_ops);
 
 /* ---- trainer-side twin: the differentiable batched portfolio reward of the
  * PG / A2C agents (agent/pg/pg.py:40-82 `_reward`, agent/a2c.py/a2c.py:40-82 `_loss`

@@ -191,6 +191,8 @@ bool replay_gather(const float* series, int32_t T, int32_t N, int32_t F, int32_t
 // pmenv_replay_gather_seq: the window stores' cache-policy bits (< 0: the product's rule)
 // and the elements per chunk (0: the product's rule)
 void replay_seq_knobs(int* policy, int* chunk);
+// pmenv_ind_*: the recurrences' form (ind_plan.h IndForm; < 0: the product's rule)
+int ind_form();
 bool rollout_gather(const float* series, int32_t T, int32_t N, int32_t F, int32_t W, const int32_t* start,
                     const float* weights, int32_t T_rec, int32_t B, int32_t ring_mode, const int32_t* t_idx,
                     const int32_t* env, int32_t S, float* s, hipStream_t stream, int* rc);

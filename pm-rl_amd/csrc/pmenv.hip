@@ -6,7 +6,7 @@
 // rollout.h (GAE, moments), replay.h (replay gather, metrics), metrics_env.h (the metrics
 // per episode) and trainer.h (batched reward); the step's launchers in launch.h, the
 // handle in handle.h, features.h (fractional differencing, column scalers; their plan in
-// ffd_plan.h), its shape plan — which kernel a step takes, in which geometry — in
+// ffd_plan.h), indicators.h (the technical indicators; their plan in ind_plan.h), its shape plan — which kernel a step takes, in which geometry — in
 // step_plan.h, the sample gathers' kernel choice in replay_plan.h (both host only).
 //
 // Every entry point enqueues on the caller's stream and never synchronises, allocates or
@@ -32,6 +32,8 @@
 #include "features.h"
 #include "ffd_plan.h"
 #include "handle.h"
+#include "ind_plan.h"
+#include "indicators.h"
 #include "launch.h"
 #include "metrics_env.h"
 #include "prio.h"
@@ -1116,6 +1118,94 @@ int pmenv_scale_apply(const float* x, int32_t T, int32_t C, int32_t method, cons
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
 
+// ---- the technical indicators: ind_plan.h holds the ops' parameters and every decision,
+// indicators.h the kernels; the four entry points read the same IndPlan
+int pmenv_ind_layout(const pmenv_ind_op* ops, int32_t n_ops, int32_t* n_out, int32_t* lookback) {
+    return ind_layout(ops, n_ops, n_out, lookback);
+}
+
+size_t pmenv_ind_workspace(int32_t T, int32_t N, const pmenv_ind_op* ops, int32_t n_ops) {
+    const IndPlan plan = ind_plan(T, N, ops, n_ops, pmenv_tools::ind_form());
+    return plan.ok ? plan.work_bytes : 0;
+}
+
+const char* pmenv_ind_path(int32_t T, int32_t N, const pmenv_ind_op* ops, int32_t n_ops) {
+    thread_local char text[512];
+    ind_plan_describe(ind_plan(T, N, ops, n_ops, pmenv_tools::ind_form()), text, sizeof(text));
+    return text;
+}
+
+int pmenv_ind_apply(const float* bars, int32_t T, int32_t N, int32_t C, const int32_t chan[5], const pmenv_ind_op* ops,
+                    int32_t n_ops, float* out, int32_t ldo, int32_t col0, void* work, size_t work_bytes,
+                    hipStream_t stream) {
+    if (!bars || !chan || !out || C < 1) return PMENV_ERR_ARG;
+    const IndPlan plan = ind_plan(T, N, ops, n_ops, pmenv_tools::ind_form());
+    if (!plan.ok || col0 < 0 || (int64_t)col0 + plan.K > ldo) return PMENV_ERR_ARG;
+    for (int i = 0; i < 5; ++i)
+        if (((plan.need >> i) & 1u) && (chan[i] < 0 || chan[i] >= C)) return PMENV_ERR_ARG;
+    if (plan.work_bytes > 0 && (!work || work_bytes < plan.work_bytes || ((uintptr_t)work & 7u))) return PMENV_ERR_ARG;
+    if (((uintptr_t)bars | (uintptr_t)out) & 3u) return PMENV_ERR_ALIGN;
+    const size_t R = (size_t)(T - plan.L);
+    const uintptr_t o0 = (uintptr_t)out, o1 = o0 + R * (size_t)N * (size_t)ldo * sizeof(float);
+    const uintptr_t x0 = (uintptr_t)bars, x1 = x0 + (size_t)T * (size_t)N * (size_t)C * sizeof(float);
+    if (o0 < x1 && x0 < o1) return PMENV_ERR_ARG;
+
+    for (int w = 0; w < plan.n_walks; ++w) {
+        const IndWalk& wk = plan.walk[w];
+        IndScanArgs a;
+        memset(&a, 0, sizeof(a));
+        a.bars = bars;
+        a.out = out;
+        a.rec = (double*)work;
+        a.T = T; a.N = N; a.C = C; a.ldo = ldo; a.L = plan.L;
+        for (int i = 0; i < 5; ++i) a.ch[i] = chan[i];
+        a.mask = wk.mask;
+        a.need = wk.need;
+        for (int k = 0; k < kIndKinds; ++k) {
+            for (int j = 0; j < 3; ++j) a.p[k][j] = wk.p[k][j];
+            a.col[k] = col0 + wk.col[k];
+        }
+        a.seg_len = plan.seg_len;
+        a.n_seg = plan.n_seg;
+        if (plan.form == kIndSplit) {
+            for (int i = 0; i < kIndSlots; ++i) a.apow[i] = ind_pow(ind_slot_coef(wk, i), plan.seg_len);
+            const dim3 all(plan.scan_grid, (unsigned)plan.n_seg), rest(plan.scan_grid, (unsigned)(plan.n_seg - 1));
+            ind_scan_split_kernel<1><<<all, 64, 0, stream>>>(a);
+            if (wk.mask & kIndLevel2Mask) {             // the level-2 kinds alone: their level 1, then their level 2
+                IndScanArgs b = a;
+                b.mask = wk.mask & kIndLevel2Mask;
+                ind_scan_split_kernel<2><<<rest, 64, 0, stream>>>(b);
+            }
+            ind_scan_split_kernel<3><<<rest, 64, 0, stream>>>(a);
+        } else {
+            ind_scan_seq_kernel<<<plan.scan_grid, 64, 0, stream>>>(a);
+        }
+    }
+    for (int w = 0; w < plan.n_window; ++w) {
+        const IndWindowOp& op = plan.window[w];
+        IndWinArgs a;
+        memset(&a, 0, sizeof(a));
+        a.bars = bars;
+        a.out = out;
+        a.fastk = (double*)((char*)work + plan.fastk_off);
+        a.T = T; a.N = N; a.C = C; a.ldo = ldo; a.L = plan.L;
+        for (int i = 0; i < 5; ++i) a.ch[i] = chan[i];
+        a.col = col0 + op.col;
+        for (int j = 0; j < 3; ++j) a.p[j] = op.p[j];
+        a.f[0] = op.f[0];
+        a.f[1] = op.f[1];
+        if (op.kind == PMENV_IND_BBANDS) {
+            ind_window_kernel<PMENV_IND_BBANDS><<<plan.window_grid, kIndWindowBlock, 0, stream>>>(a);
+        } else if (op.kind == PMENV_IND_CCI) {
+            ind_window_kernel<PMENV_IND_CCI><<<plan.window_grid, kIndWindowBlock, 0, stream>>>(a);
+        } else {
+            ind_fastk_kernel<<<plan.fastk_grid, kIndWindowBlock, 0, stream>>>(a);
+            ind_window_kernel<PMENV_IND_STOCH><<<plan.window_grid, kIndWindowBlock, 0, stream>>>(a);
+        }
+    }
+    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
 // ---- the sample gathers: replay_plan.h decides the kernel and its geometry, the entry points
 // validate, plan and launch; pmenv_replay_path names the plan
 const char* pmenv_replay_path(int32_t kind, int32_t N, int32_t F, int32_t W, int32_t n, int32_t S, int32_t aligned,
@@ -1635,6 +1725,7 @@ __attribute__((weak, noinline)) bool replay_gather(const float*, int32_t, int32_
     return false;
 }
 __attribute__((weak, noinline)) void replay_seq_knobs(int*, int*) {}
+__attribute__((weak, noinline)) int ind_form() { return -1; }
 __attribute__((weak, noinline)) bool rollout_gather(const float*, int32_t, int32_t, int32_t, int32_t, const int32_t*,
                                                     const float*, int32_t, int32_t, int32_t, const int32_t*,
                                                     const int32_t*, int32_t, float*, hipStream_t, int*) {

@@ -57,6 +57,12 @@ PHASE_SCALAR = 1
 PHASE_ADVANCE = 2
 STEP_PATHS = {"auto": 0, "one_launch": 1, "two_launch": 2, "flat": 3, "relay": 4}
 SCALE_METHODS = {"minmax": 0, "standard": 1}   # pmenv_scale_method
+IND_KINDS = {"ema": 0, "bbands": 1, "macd": 2, "atr": 3, "rsi": 4, "adx": 5, "dx": 6, "stoch": 7, "cci": 8,
+             "obv": 9, "adosc": 10}            # pmenv_ind_kind
+
+
+class PmenvIndOp(ctypes.Structure):            # pmenv_ind_op
+    _fields_ = [("kind", ctypes.c_int32), ("p", ctypes.c_int32 * 3), ("f", ctypes.c_double * 2)]
 REPLAY_KINDS = {"one_step": 0, "nstep": 1, "seq": 2, "rollout": 3}   # pmenv_replay_kind
 
 
@@ -144,6 +150,10 @@ SIGNATURES = [
     ("pmenv_scale_workspace", _SZ, [_I32, _I32]),
     ("pmenv_scale_fit", ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P, _SZ, _P]),
     ("pmenv_scale_apply", ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P, _P]),
+    ("pmenv_ind_layout", ctypes.c_int, [_P, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
+    ("pmenv_ind_workspace", _SZ, [_I32, _I32, _P, _I32]),
+    ("pmenv_ind_apply", ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _P, _SZ, _P]),
+    ("pmenv_ind_path", ctypes.c_char_p, [_I32, _I32, _P, _I32]),
 ]
 
 _lib = None

@@ -1,9 +1,12 @@
 """The loader's feature stages on the device ("needed for real-data configs").
 
 The reference never feeds its env raw bars. Its loader turns them into observation
-channels in four stages:
+channels in five stages:
 
     reference                                              here
+    InstrumentPool.add_indicators (data_loader.py:37,      indicators (pmenv_ind_apply: the eleven of
+      instrument.py:207-232: TA-Lib on the host, once        config/base.py:30-44 over every column in f64,
+      per ticker, clipped by the largest lookback)           written into the combined channel tensor)
     prices = close[1:] / close[:-1]; rows 1:               build() step 1 — the relatives become a table
       (data/instrument.py:79-80)                             of their own, MarketSeries.relatives
     FixedFracDiff.fit_transform (data/ffd.py:36-57,        ffd_weights (host, ffd_plan.h) + frac_diff
@@ -18,9 +21,13 @@ After those stages the close column is a differenced value scaled to 0..1: divid
 of them is no price relative, so a series built here carries its relatives, and the step
 and the compact rollout buffer read that table (trading_env.py, rollout_buffer.py).
 
-Out of scope: the TA-Lib indicators and the ADF search for d (ffd.py:59-78) — the caller
-supplies indicator columns as channels and the d values, as the reference loads them from
-its d_opt pickles.
+The indicators follow the definitions of include/pmenv.h (TA-Lib's default algorithms
+restated; DESIGN.md "Technical indicators" lists them and the two deliberate deviations), so
+a real-data user needs neither TA-Lib nor a host round trip, and a device-resident series
+gets its indicator channels where it lies.
+
+Out of scope: the ADF search for d (ffd.py:59-78) — the caller supplies the d values, as the
+reference loads them from its d_opt pickles.
 """
 import ctypes
 
@@ -146,13 +153,134 @@ def scale(x, method="minmax", stats=None, out=None):
     return out, stats
 
 
-def build(raw, d, thres=1e-5, train_ratio=0.8, scaler="minmax", close_channel=3, device=None):
+# name -> (period parameters in pmenv_ind_op.p order, float parameters in .f order, TA-Lib's
+# defaults, TA-Lib's output names, the moving-average-type parameters: 0 (SMA) only)
+_IND = {
+    "ema": (("timeperiod",), (), {"timeperiod": 30}, ("real",), ()),
+    "bbands": (("timeperiod",), ("nbdevup", "nbdevdn"), {"timeperiod": 5, "nbdevup": 2.0, "nbdevdn": 2.0},
+               ("upperband", "middleband", "lowerband"), ("matype",)),
+    "macd": (("fastperiod", "slowperiod", "signalperiod"), (), {"fastperiod": 12, "slowperiod": 26, "signalperiod": 9},
+             ("macd", "macdsignal", "macdhist"), ()),
+    "atr": (("timeperiod",), (), {"timeperiod": 14}, ("real",), ()),
+    "rsi": (("timeperiod",), (), {"timeperiod": 14}, ("real",), ()),
+    "adx": (("timeperiod",), (), {"timeperiod": 14}, ("real",), ()),
+    "dx": (("timeperiod",), (), {"timeperiod": 14}, ("real",), ()),
+    "stoch": (("fastk_period", "slowk_period", "slowd_period"), (),
+              {"fastk_period": 5, "slowk_period": 3, "slowd_period": 3}, ("slowk", "slowd"),
+              ("slowk_matype", "slowd_matype")),
+    "cci": (("timeperiod",), (), {"timeperiod": 14}, ("real",), ()),
+    "obv": ((), (), {}, ("real",), ()),
+    "adosc": (("fastperiod", "slowperiod"), (), {"fastperiod": 3, "slowperiod": 10}, ("real",), ()),
+}
+
+
+def indicator_ops(spec):
+    """spec, a list of (name, params) pairs (a list, not the reference's dict, which keeps one
+    "ema" only) -> (pmenv_ind_op array, output names). Names are case-insensitive, missing
+    parameters take TA-Lib's defaults; an output called "real" takes the indicator's name and
+    every name gets "_" + the given parameter values joined by "_" (instrument.py:227-229):
+    "ema_30", "upperband_20", "macd_" for empty params. Only SMA smoothing: a matype other
+    than 0 is refused."""
+    spec = list(spec)
+    if not spec:
+        raise ValueError("an indicator spec needs at least one (name, params) pair")
+    ops = (_abi.PmenvIndOp * len(spec))()
+    names = []
+    for op, item in zip(ops, spec):
+        name, params = item
+        key = str(name).lower()
+        if key not in _IND:
+            raise ValueError(f"unknown indicator {name!r}; one of {sorted(_IND)}")
+        periods, floats, defaults, outs, matypes = _IND[key]
+        params = dict(params or {})
+        for k, v in params.items():
+            if k in matypes:
+                if v != 0:
+                    raise ValueError(f"{key}: {k}={v!r}: only SMA smoothing (0) is supported")
+            elif k not in defaults:
+                raise ValueError(f"{key}: unknown parameter {k!r}")
+        full = dict(defaults, **{k: v for k, v in params.items() if k in defaults})
+        op.kind = _abi.IND_KINDS[key]
+        for i, k in enumerate(periods):
+            if int(full[k]) != full[k]:
+                raise ValueError(f"{key}: {k} must be an integer")
+            op.p[i] = int(full[k])
+        for i, k in enumerate(floats):
+            op.f[i] = float(full[k])
+        suffix = "_" + "_".join(f"{v}" for v in params.values())
+        names += [(key if o == "real" else o) + suffix for o in outs]
+    return ops, names
+
+
+def indicator_layout(spec):
+    """(K, lookback, names) of a spec: the output columns and the rows the stage clips. Host only."""
+    ops, names = indicator_ops(spec)
+    k, look = ctypes.c_int32(0), ctypes.c_int32(0)
+    _abi.check(_abi.load().pmenv_ind_layout(ops, len(ops), ctypes.byref(k), ctypes.byref(look)), None,
+               "pmenv_ind_layout")
+    return k.value, look.value, names
+
+
+def indicator_path(T, N, spec):
+    """The kernels pmenv_ind_apply launches for bars [T, N, .] and their geometry, in launch
+    order: [(name, {key: value})], e.g. [("ind_scan_split_kernel", {"walks": 1, "seg": 78,
+    "segs": 64, "grid": (8, 64), "block": 64}), ("ind_window_kernel", {...})]; [] for a
+    refused shape. Host only."""
+    ops, _ = indicator_ops(spec)
+    text = _abi.load().pmenv_ind_path(int(T), int(N), ops, len(ops)).decode()
+    out = []
+    for part in text.split(" | ") if text else ():
+        name, *fields = part.split(" ")
+        geo = dict(f.split("=") for f in fields)
+        out.append((name, {k: tuple(int(x) for x in v.split("x")) if "x" in v else int(v) for k, v in geo.items()}))
+    return out
+
+
+def indicators(bars, spec, channels=(0, 1, 2, 3, 4), out=None, col0=0):
+    """The technical indicators of bars [T, N, C] (device, f32, contiguous): spec is a list of
+    (name, params) pairs, channels the indices of open, high, low, close and volume (-1 for
+    one no requested op reads). Returns (cols [T - L, N, K], names, L): L is the largest
+    lookback of the spec and every op is aligned to series row L + r. out, if given, is a
+    contiguous [T - L, N, ldo] tensor whose channels col0 .. col0 + K - 1 are written (the
+    others are left alone); cols is then that view."""
+    lib = _abi.load()
+    if not torch.is_tensor(bars) or not bars.is_cuda or bars.dtype != torch.float32 or not bars.is_contiguous() \
+            or bars.dim() != 3:
+        raise ValueError("bars must be a contiguous float32 [T, N, C] device tensor")
+    ops, names = indicator_ops(spec)
+    K, L, _ = indicator_layout(spec)
+    T, N, C = bars.shape
+    if T <= L:
+        raise ValueError(f"the longest lookback ({L} rows) leaves no row of a {T}-row series")
+    chan = (ctypes.c_int32 * 5)(*[int(c) for c in channels])
+    if out is None:
+        out = torch.empty(T - L, N, K, dtype=torch.float32, device=bars.device)
+        col0 = 0
+    elif out.dim() != 3 or tuple(out.shape[:2]) != (T - L, N) or out.dtype != torch.float32 or \
+            not out.is_contiguous() or out.device != bars.device:
+        raise ValueError(f"out must be a contiguous float32 [{T - L}, {N}, ldo] tensor on {bars.device}")
+    nbytes = lib.pmenv_ind_workspace(T, N, ops, len(ops))
+    work = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=bars.device)
+    _abi.check(lib.pmenv_ind_apply(_ptr(bars), T, N, C, chan, ops, len(ops), _ptr(out), out.shape[2], int(col0),
+                                   _ptr(work), nbytes, _stream(bars.device)), None, "pmenv_ind_apply")
+    return out[:, :, col0:col0 + K], names, L
+
+
+_indicators = indicators      # build()'s `indicators` argument shadows the function
+
+
+def build(raw, d, thres=1e-5, train_ratio=0.8, scaler="minmax", close_channel=3, device=None, indicators=None,
+          channels=(0, 1, 2, 3, 4), channel_names=None):
     """The reference loader's order on the device. raw [T, N, C] (numpy or torch): C market
     channels per asset, raw prices in `close_channel`; d: a scalar, [C] or [N, C] orders of
     differencing, 0 = leave the channel alone (the reference's feat_ignore columns);
     scaler "minmax", "standard" or None.
 
       1. relatives[t] = close[t+1] / close[t] and the features are rows 1: (instrument.py:79-80)
+      1b. with `indicators` (a spec as indicators() takes it; `channels` names the OHLCV
+         channels): the K indicator columns are appended after the C raw channels, and features
+         and relatives lose the first `lookback` rows (instrument.py:207-232); d then
+         broadcasts over the C + K channels. None (the default) skips the stage.
       2. FFD of the features; features and relatives lose the first max_width rows, the one
          largest width over all assets and channels (ffd.py:81-88, instrument_pool.py:350-359)
       3. split at int(train_ratio * len) with a purge of max_width rows in front of the test
@@ -160,7 +288,9 @@ def build(raw, d, thres=1e-5, train_ratio=0.8, scaler="minmax", close_channel=3,
       4. each part scaled on its own, per (asset, channel) column (instrument.py:331-336)
 
     Returns (train, test): MarketSeries whose .relatives [T', N] row t belongs to bars[t],
-    with .widths (int32 [N, C]) and .max_width.
+    with .widths (int32 [N, C]) and .max_width; with `indicators` also .channel_names (the raw
+    channels' names, `channel_names` or "c0" .. , then the indicators') and
+    .indicator_lookback.
 
     Two defects of the reference are not reproduced: Instrument.stationary clips the
     features by the FFD width but leaves `prices` at full length, so row t of the relatives
@@ -176,6 +306,19 @@ def build(raw, d, thres=1e-5, train_ratio=0.8, scaler="minmax", close_channel=3,
     close = r[:, :, close_channel]
     rel = (close[1:] / close[:-1]).contiguous()                        # 1
     feats = r[1:].contiguous()
+    names, look = None, 0
+    if indicators is not None:                                         # 1b
+        K, look, ind_names = indicator_layout(indicators)
+        if T - 1 <= look:
+            raise ValueError(f"the longest lookback ({look} rows) leaves no row of a {T - 1}-row series")
+        both = torch.empty(T - 1 - look, N, C + K, dtype=torch.float32, device=dev)
+        both[:, :, :C] = feats[look:]
+        _indicators(feats, indicators, channels, out=both, col0=C)
+        raw_names = list(channel_names) if channel_names is not None else [f"c{i}" for i in range(C)]
+        if len(raw_names) != C:
+            raise ValueError("channel_names must name the C raw channels")
+        names = raw_names + ind_names
+        feats, rel = both, rel[look:]
     x, widths, mw = frac_diff(feats, d, thres)                         # 2
     rel = rel[mw:]
     n = x.shape[0]
@@ -187,5 +330,7 @@ def build(raw, d, thres=1e-5, train_ratio=0.8, scaler="minmax", close_channel=3,
             scale(bars, scaler, out=bars)
         s = MarketSeries(bars, device=dev, relatives=rel[lo:hi].contiguous())
         s.widths, s.max_width = widths, mw
+        if names is not None:
+            s.channel_names, s.indicator_lookback = names, look
         parts.append(s)
     return tuple(parts)

@@ -1002,6 +1002,13 @@ bool rollout_gather(const float* series, int32_t T, int32_t N, int32_t F, int32_
 
 // metrics: PMENV_METRICS_WALK (the thread-per-env walk), PMENV_METRICS_FUSED=0 (two
 // launches), PMENV_METRICS_SEG_FIRST=0 (turnover blocks dispatched first)
+// PMENV_IND_FORM = 0 / 1: the indicators' recurrences in the sequential / the split form at any
+// column count (tools/bench_indicators.py times both at one shape)
+int ind_form() {
+    const char* v = knob("PMENV_IND_FORM");
+    return v && *v ? atoi(v) : -1;
+}
+
 bool metrics(const double* returns, const double* values, const float* weights, int32_t T, int32_t B, int32_t N,
              double risk_free_rate, double periods, double* out, hipStream_t stream, int* rc) {
     const bool walk = knob("PMENV_METRICS_WALK") != nullptr;
