@@ -51,7 +51,9 @@ extern "C" {
  *    pmenv_ffd_weights, pmenv_ffd_apply, pmenv_ffd_path, pmenv_scale_workspace, pmenv_scale_fit
  *    and pmenv_scale_apply, the loader's feature stages on the device, likewise;
  *    pmenv_ind_layout, pmenv_ind_workspace, pmenv_ind_apply and pmenv_ind_path, the loader's
- *    technical indicators on the device, likewise) */
+ *    technical indicators on the device, likewise; pmenv_ffd_table, pmenv_adf,
+ *    pmenv_adf_workspace, pmenv_adf_path, pmenv_adf_maxlag, pmenv_adf_pvalue and
+ *    pmenv_adf_search_update, the search for the orders of differencing, likewise) */
 #define PMENV_ABI_VERSION 4
 
 /* Opaque HIP stream (identical to HIP's own typedef); NULL = default stream. */
@@ -533,6 +535,87 @@ int pmenv_ind_apply(const float* bars, int32_t T, int32_t N, int32_t C, const in
  * segment and segments. "" for a refused shape. Host only; thread-local, valid until the
  * thread's next call; read from the plan pmenv_ind_apply dispatches on. */
 const char* pmenv_ind_path(int32_t T, int32_t N, const pmenv_ind_op* ops, int32_t n_ops);
+
+/* ---- the search for the orders of differencing on the device (data/ffd.py:59-78,
+ * FixedFracDiff.fit: per (ticker, feature) column a bisection of d whose every probe is one
+ * conv1d (:69) and one statsmodels adfuller call (:70) on the host; the reference caches the
+ * result in its d_opt pickles). statsmodels is not a dependency and parity with it is not
+ * pinned: the definitions below are the contract (DESIGN.md "The ADF search" restates them).
+ *
+ * The ADF statistic of a column x[0 .. n-1] (widened to f64) is adfuller(x) at its defaults,
+ * regression "c", autolag "AIC": D[i] = x[i+1] - x[i]; the model of lag k on rows i = s .. n-2
+ * is D[i] = alpha + beta x[i] + sum_{j=1..k} gamma_j D[i-j] + eps. maxlag = min(n / 2 - 2,
+ * ceil(12 (n / 100)^(1/4))), the ceiling taken in integers (the smallest m with 100 m^4 >=
+ * 20736 n); a caller's maxlag >= 0 replaces the rule and is clamped to n / 2 - 2. With autolag
+ * the lags k = 0 .. maxlag are all fitted on the common rows s = maxlag, nobs = n - 1 - maxlag,
+ * AIC_k = nobs ln(ssr_k / nobs) + 2 (k + 2), and usedlag is the smallest k of the smallest AIC;
+ * without it usedlag = maxlag. The final fit has lag usedlag on rows s = usedlag, nobs = n - 1 -
+ * usedlag, p = usedlag + 2 parameters, and stat = beta / sqrt(ssr / (nobs - p) [(X'X)^-1]_beta).
+ * The p-value is MacKinnon's (1994) for a constant and one series: 1 above 2.74, 0 below
+ * -18.83, Phi(2.1659 + 1.4412 s + 0.038269 s^2) up to -1.61 and Phi(1.7339 + 0.93202 s -
+ * 0.12745 s^2 - 0.010368 s^3) above, Phi(z) = erfc(-z / sqrt 2) / 2 in f64. ---- */
+typedef enum pmenv_adf_status {
+    PMENV_ADF_OK = 0,
+    PMENV_ADF_TOO_SHORT = 1,   /* n < 16: stat and pvalue NaN, usedlag and nobs 0 */
+    PMENV_ADF_DEGENERATE = 2   /* a value that is not finite, a pivot that is not positive or an ssr <= 0 in any
+                                  fit (a constant column, a pure ramp): stat and pvalue NaN, usedlag and nobs 0 */
+} pmenv_adf_status;
+/* ffd.py:38-47 for every column at once, on the device: d [C] f64 -> taps [cap, C] f32
+ * (tap-major, rows >= width[c] zeroed) and width [C] int32, the taps and the width of
+ * pmenv_ffd_weights(d[c], thres, T) bit for bit (one lane per column runs the same f32 factors
+ * and f64 running product; min(width, cap) taps are written). A d[c] that is negative or not
+ * finite gives width 0. PMENV_ERR_ARG: NULL d or width, T < 2, C < 1, cap < 0, NULL taps with
+ * cap > 0, thres negative or not finite. d 8-B, taps and width 4-B aligned. No allocation, no
+ * synchronisation, capturable. */
+int pmenv_ffd_table(const double* d, double thres, int32_t T, int32_t C, int32_t cap, float* taps, int32_t* width,
+                    hipStream_t stream);
+/* The lag bound of a column of n rows (the integer rule above; maxlag < 0: the default) and
+ * the p-value of a statistic, as the kernels compute them. Host only. */
+int32_t pmenv_adf_maxlag(int64_t n, int32_t maxlag);
+double pmenv_adf_pvalue(double stat);
+/* Device scratch of one pmenv_adf call in bytes: 2 kcap + 7 doubles per column, kcap the lag
+ * bound of a column of R rows. 0 for a refused shape. */
+size_t pmenv_adf_workspace(int32_t R, int32_t C, int32_t maxlag);
+/* ffd.py:70 (adfuller(...)[1]) for every column of y [R, C] f32 (row stride ld >= C floats) in
+ * two launches. Column c is rows first[c] .. R-1 (first NULL: 0; clamped to [0, R]), so
+ * columns of unequal length — the outputs of filters of unequal width — share one tensor.
+ * maxlag < 0: the default rule per column; autolag 0: usedlag = maxlag. stat, pvalue f64 [C],
+ * usedlag, nobs, status (pmenv_adf_status) int32 [C].
+ * The fits are solved through the normal equations in f64: level and differences are shifted
+ * by constants near their means (the mean of 64 evenly spread rows; (x[n-1] - x[0]) / (n - 1)), the Gram matrix of [level, D_-1 .. D_-maxlag | D] is
+ * centred by the column sums over the fit's rows (the constant absorbs the means) and factored
+ * once (Cholesky); the models are nested in that order, so every ssr_k comes from that one
+ * factor. The final fit adds the maxlag - usedlag earlier rows and factors once more. Every sum
+ * is one chain in a fixed order: a column's outputs depend on no other column, not on C, ld or
+ * first[c], and not on what work held. A NaN or inf touches its own column only (DEGENERATE).
+ * PMENV_ERR_ARG: a NULL pointer other than first, R < 1, C < 1, ld < C, maxlag > 64 or a
+ * default lag bound above 64 (R > 80,908), work NULL, not 8-B aligned or below
+ * pmenv_adf_workspace. PMENV_ERR_ALIGN: y, first or an int32 output not 4-B, stat or pvalue
+ * not 8-B aligned. No allocation, no synchronisation, capturable. */
+int pmenv_adf(const float* y, int32_t R, int32_t C, int32_t ld, const int32_t* first, int32_t maxlag,
+              int32_t autolag, double* stat, double* pvalue, int32_t* usedlag, int32_t* nobs, int32_t* status,
+              void* work, size_t work_bytes, hipStream_t stream);
+/* The kernels of that call in launch order with their geometry, e.g.
+ *   "adf_sums_kernel tile=8 chunk=256 kcap=17 grid=17 block=512 | adf_solve_kernel kcap=17 lds=3952 grid=130 block=64"
+ * tile: columns per workgroup of the sums (one wave each), chunk: rows per staging step, kcap:
+ * the largest lag bound of the call, lds: dynamic LDS bytes. "" for a refused shape. Host
+ * only; thread-local, valid until the thread's next call. */
+const char* pmenv_adf_path(int32_t R, int32_t C, int32_t maxlag);
+/* One round of ffd.py:59-78 for every column, one thread each, on the state low, high, d_opt
+ * (f64 [C]; 0, 1, 0 at the start) and active, evals, status (int32 [C]). pvalue NULL: the
+ * first round, nothing probed yet. Otherwise an active column's probe at d_opt gave pvalue[c],
+ * stat[c], adf_status[c]: status[c] takes the probe's status and last [2, C] (may be NULL) its
+ * pvalue and stat; TOO_SHORT counts as p = 1 (the reference would raise: the one deliberate
+ * deviation); p > 0.05 sets low = d_opt, p < 0.049 sets high = d_opt, anything else (the band,
+ * a NaN) ends the column at d_opt (:73-78). A column still active takes d_mid = (low + high) /
+ * 2: d_mid < thres ends it at d_opt = 0 (:62-64), |d_opt - d_mid| < thres ends it where it is
+ * (:65-66), otherwise d_opt = d_mid is its next probe and evals[c] grows by one. d[c] = d_opt
+ * for every column, active or not. Every d is a dyadic rational: the trajectory is exact.
+ * PMENV_ERR_ARG: a NULL state pointer or d, C < 1, thres not positive, pvalue without stat and
+ * adf_status. No allocation, no synchronisation, capturable. */
+int pmenv_adf_search_update(const double* pvalue, const double* stat, const int32_t* adf_status, double thres,
+                            int32_t C, double* low, double* high, double* d_opt, int32_t* active, int32_t* evals,
+                            int32_t* status, double* last, double* d, hipStream_t stream);
 
 /* ---- trainer-side twin: the differentiable batched portfolio reward of the
  * PG / A2C agents (agent/pg/pg.py:40-82 `_reward`, agent/a2c.py/a2c.py:40-82 `_loss`

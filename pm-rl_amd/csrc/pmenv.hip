@@ -6,7 +6,8 @@
 // rollout.h (GAE, moments), replay.h (replay gather, metrics), metrics_env.h (the metrics
 // per episode) and trainer.h (batched reward); the step's launchers in launch.h, the
 // handle in handle.h, features.h (fractional differencing, column scalers; their plan in
-// ffd_plan.h), indicators.h (the technical indicators; their plan in ind_plan.h), its shape plan — which kernel a step takes, in which geometry — in
+// ffd_plan.h), indicators.h (the technical indicators; their plan in ind_plan.h), adf.h (the
+// search for the orders of differencing; its plan in adf_plan.h), its shape plan — which kernel a step takes, in which geometry — in
 // step_plan.h, the sample gathers' kernel choice in replay_plan.h (both host only).
 //
 // Every entry point enqueues on the caller's stream and never synchronises, allocates or
@@ -27,6 +28,8 @@
 #include <type_traits>
 
 #include "../../include/pmenv.h"
+#include "adf.h"
+#include "adf_plan.h"
 #include "data.h"
 #include "episode.h"
 #include "features.h"
@@ -1115,6 +1118,62 @@ int pmenv_scale_apply(const float* x, int32_t T, int32_t C, int32_t method, cons
     if ((((uintptr_t)x | (uintptr_t)y) & 3u) || ((uintptr_t)stats & 7u)) return PMENV_ERR_ALIGN;
     const dim3 grid((unsigned)(((int64_t)T + 31) / 32), (unsigned)((C + 63) / 64));
     scale_apply_kernel<<<grid, 256, 0, stream>>>(x, T, C, method == PMENV_SCALE_STANDARD, stats, y);
+    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
+// ---- the search for the orders of differencing: adf_plan.h holds the lag rule, the p-value and
+// the geometry, adf.h the kernels
+int pmenv_ffd_table(const double* d, double thres, int32_t T, int32_t C, int32_t cap, float* taps, int32_t* width,
+                    hipStream_t stream) {
+    if (!d || !width || T < 2 || C < 1 || cap < 0 || (cap > 0 && !taps) || !(thres >= 0.0) || !isfinite(thres))
+        return PMENV_ERR_ARG;
+    if (((uintptr_t)d & 7u) || (((uintptr_t)taps | (uintptr_t)width) & 3u)) return PMENV_ERR_ALIGN;
+    const unsigned grid = (unsigned)(((int64_t)C + kAdfTableBlock - 1) / kAdfTableBlock);
+    ffd_table_kernel<<<grid, kAdfTableBlock, 0, stream>>>(d, thres, T, C, cap, taps, width);
+    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
+int32_t pmenv_adf_maxlag(int64_t n, int32_t maxlag) { return (int32_t)adf_maxlag(n, maxlag); }
+
+double pmenv_adf_pvalue(double stat) { return adf_pvalue(stat); }
+
+size_t pmenv_adf_workspace(int32_t R, int32_t C, int32_t maxlag) { return adf_plan(R, C, C, maxlag).work_bytes; }
+
+const char* pmenv_adf_path(int32_t R, int32_t C, int32_t maxlag) {
+    thread_local char text[256];
+    adf_plan_describe(adf_plan(R, C, C, maxlag), text, sizeof(text));
+    return text;
+}
+
+int pmenv_adf(const float* y, int32_t R, int32_t C, int32_t ld, const int32_t* first, int32_t maxlag, int32_t autolag,
+              double* stat, double* pvalue, int32_t* usedlag, int32_t* nobs, int32_t* status, void* work,
+              size_t work_bytes, hipStream_t stream) {
+    if (!y || !stat || !pvalue || !usedlag || !nobs || !status) return PMENV_ERR_ARG;
+    const AdfPlan plan = adf_plan(R, C, ld, maxlag);
+    if (!plan.ok || !work || ((uintptr_t)work & 7u) || work_bytes < plan.work_bytes) return PMENV_ERR_ARG;
+    if ((((uintptr_t)y | (uintptr_t)first | (uintptr_t)usedlag | (uintptr_t)nobs | (uintptr_t)status) & 3u) ||
+        (((uintptr_t)stat | (uintptr_t)pvalue) & 7u))
+        return PMENV_ERR_ALIGN;
+    adf_sums_kernel<<<plan.sums_grid, plan.sums_block, 0, stream>>>(y, first, R, C, ld, maxlag, plan.rec,
+                                                                    (double*)work);
+    adf_solve_kernel<<<plan.solve_grid, plan.solve_block, plan.solve_lds, stream>>>(
+        y, first, R, C, ld, maxlag, autolag != 0, plan.kcap, plan.rec, (const double*)work, stat, pvalue, usedlag, nobs,
+        status);
+    return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
+}
+
+int pmenv_adf_search_update(const double* pvalue, const double* stat, const int32_t* adf_status, double thres,
+                            int32_t C, double* low, double* high, double* d_opt, int32_t* active, int32_t* evals,
+                            int32_t* status, double* last, double* d, hipStream_t stream) {
+    if (!low || !high || !d_opt || !active || !evals || !status || !d || C < 1 || !(thres > 0.0) ||
+        (pvalue && (!stat || !adf_status)))
+        return PMENV_ERR_ARG;
+    if ((((uintptr_t)pvalue | (uintptr_t)stat | (uintptr_t)low | (uintptr_t)high | (uintptr_t)d_opt | (uintptr_t)last |
+          (uintptr_t)d) & 7u) ||
+        (((uintptr_t)adf_status | (uintptr_t)active | (uintptr_t)evals | (uintptr_t)status) & 3u))
+        return PMENV_ERR_ALIGN;
+    adf_search_update_kernel<<<(unsigned)(((int64_t)C + 255) / 256), 256, 0, stream>>>(
+        pvalue, stat, adf_status, thres, C, low, high, d_opt, active, evals, status, last, d);
     return hipGetLastError() == hipSuccess ? PMENV_OK : PMENV_ERR_HIP;
 }
 

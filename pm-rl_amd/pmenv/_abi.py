@@ -21,7 +21,8 @@ PMENV_ABI_VERSION = 4   # 2: pmenv_window_written / pmenv_state_written; cfg def
                         #    pmenv_replay_valid_build / _select, pmenv_replay_gather_nstep_env /
                         #    _seq_env and pmenv_prio_fill_env likewise; pmenv_rollout_gather_env and
                         #    pmenv_rollout_gather_env_path likewise; pmenv_step_path_for and
-                        #    pmenv_batch_reward_path likewise; pmenv_ffd_* and pmenv_scale_* likewise)
+                        #    pmenv_batch_reward_path likewise; pmenv_ffd_* and pmenv_scale_* likewise;
+                        #    pmenv_ffd_table and pmenv_adf_* likewise)
 
 # enums (include/pmenv.h)
 REWARD_KINDS = {"log_returns": 0, "returns": 1, "sharpe_ratio": 2, "diff_sharpe": 3}
@@ -57,6 +58,7 @@ PHASE_SCALAR = 1
 PHASE_ADVANCE = 2
 STEP_PATHS = {"auto": 0, "one_launch": 1, "two_launch": 2, "flat": 3, "relay": 4}
 SCALE_METHODS = {"minmax": 0, "standard": 1}   # pmenv_scale_method
+ADF_STATUS = {"ok": 0, "too_short": 1, "degenerate": 2}   # pmenv_adf_status
 IND_KINDS = {"ema": 0, "bbands": 1, "macd": 2, "atr": 3, "rsi": 4, "adx": 5, "dx": 6, "stoch": 7, "cci": 8,
              "obv": 9, "adosc": 10}            # pmenv_ind_kind
 
@@ -154,6 +156,13 @@ SIGNATURES = [
     ("pmenv_ind_workspace", _SZ, [_I32, _I32, _P, _I32]),
     ("pmenv_ind_apply", ctypes.c_int, [_P, _I32, _I32, _I32, _P, _P, _I32, _P, _I32, _I32, _P, _SZ, _P]),
     ("pmenv_ind_path", ctypes.c_char_p, [_I32, _I32, _P, _I32]),
+    ("pmenv_ffd_table", ctypes.c_int, [_P, ctypes.c_double, _I32, _I32, _I32, _P, _P, _P]),
+    ("pmenv_adf_maxlag", _I32, [ctypes.c_int64, _I32]),
+    ("pmenv_adf_pvalue", ctypes.c_double, [ctypes.c_double]),
+    ("pmenv_adf_workspace", _SZ, [_I32, _I32, _I32]),
+    ("pmenv_adf", ctypes.c_int, [_P, _I32, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    ("pmenv_adf_path", ctypes.c_char_p, [_I32, _I32, _I32]),
+    ("pmenv_adf_search_update", ctypes.c_int, [_P, _P, _P, ctypes.c_double, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 ]
 
 _lib = None

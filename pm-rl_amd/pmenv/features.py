@@ -12,6 +12,8 @@ channels in five stages:
     FixedFracDiff.fit_transform (data/ffd.py:36-57,        ffd_weights (host, ffd_plan.h) + frac_diff
       80-89; instrument.py:257-281; the one piece of         (pmenv_ffd_apply: every column in one launch,
       the reference that runs on the GPU, ffd.py:16-18)      per-column widths, f64 chains)
+    FixedFracDiff.fit (ffd.py:59-78: the bisection of d,   find_d (pmenv_ffd_table, pmenv_adf,
+      adfuller per probe, on the host)                       pmenv_adf_search_update: all columns per round)
     split with a purge (instrument.py:284-315,             build() step 3
       instrument_pool.py:380-403)
     MinMaxScaler / StandardScaler per (ticker, feature)    scale (pmenv_scale_fit / pmenv_scale_apply)
@@ -26,8 +28,16 @@ restated; DESIGN.md "Technical indicators" lists them and the two deliberate dev
 a real-data user needs neither TA-Lib nor a host round trip, and a device-resident series
 gets its indicator channels where it lies.
 
-Out of scope: the ADF search for d (ffd.py:59-78) — the caller supplies the d values, as the
-reference loads them from its d_opt pickles.
+The orders of differencing are searched here too (find_d; build(d="auto")): the reference's
+FixedFracDiff.fit (ffd.py:59-78) bisects d per column on the host, one conv1d and one
+statsmodels adfuller call per probe, and keeps the result in its d_opt pickles because that is
+the slow part of its loader. Here a round is four launches for all columns — the tap table of
+every column's d (pmenv_ffd_table), the FFD, a batched augmented Dickey-Fuller test
+(pmenv_adf) and the bracket update (pmenv_adf_search_update) — and nothing is read back before
+the last round. statsmodels is not a dependency and parity with it is not pinned: the ADF
+statistic and the p-value follow the definitions of include/pmenv.h (DESIGN.md "The ADF
+search"), with one deliberate deviation: a probe series too short to test (under 16 rows)
+counts as p = 1, where the reference would raise.
 """
 import ctypes
 
@@ -121,6 +131,166 @@ def frac_diff(x, d, thres=1e-5):
     wd = torch.from_numpy(widths).to(x.device)
     out = ffd_apply(x.reshape(T, -1), tab, wd, mw)
     return out.reshape((T - mw,) + cols), wd.reshape(cols), mw
+
+
+def ffd_table(d, thres, T, cap, taps=None, widths=None):
+    """pmenv_ffd_table: d float64 [C] on the device -> (taps float32 [cap, C] with the rows from
+    a column's width on zeroed, widths int32 [C]): pmenv_ffd_weights(d[c], thres, T) per column,
+    bit for bit, without a host round trip."""
+    lib = _abi.load()
+    if not torch.is_tensor(d) or not d.is_cuda or d.dtype != torch.float64 or not d.is_contiguous() or d.dim() != 1:
+        raise ValueError("d must be a contiguous float64 [C] device tensor")
+    C = d.shape[0]
+    if taps is None:
+        taps = torch.empty(cap, C, dtype=torch.float32, device=d.device)
+    if widths is None:
+        widths = torch.empty(C, dtype=torch.int32, device=d.device)
+    _abi.check(lib.pmenv_ffd_table(_ptr(d), float(thres), int(T), C, int(cap), _ptr(taps) if cap else None,
+                                   _ptr(widths), _stream(d.device)), None, "pmenv_ffd_table")
+    return taps, widths
+
+
+def adf_path(R, C, maxlag=None):
+    """The kernels pmenv_adf launches for y [R, C] and their geometry, in launch order:
+    [("adf_sums_kernel", {"tile": 8, "chunk": 256, "kcap": 17, "grid": 17, "block": 512}),
+    ("adf_solve_kernel", {"kcap": 17, "lds": 3952, "grid": 130, "block": 64})]; [] for a refused
+    shape. Host only."""
+    text = _abi.load().pmenv_adf_path(int(R), int(C), -1 if maxlag is None else int(maxlag)).decode()
+    out = []
+    for part in text.split(" | ") if text else ():
+        name, *fields = part.split(" ")
+        out.append((name, {k: int(v) for k, v in (f.split("=") for f in fields)}))
+    return out
+
+
+def adf(y, first=None, maxlag=None, autolag=True, out=None, work=None):
+    """The augmented Dickey-Fuller test of every column of y [R, ...] (device, f32; a 2-D y may
+    be a view with a row stride), adfuller(x)'s defaults as include/pmenv.h defines them:
+    constant only, AIC lag choice up to maxlag (None: the default rule per column), MacKinnon's
+    p-value. first (int32, y.shape[1:]): column c is rows first[c] .. R-1. Returns a dict of
+    stat, pvalue (float64), usedlag, nobs, status (int32; _abi.ADF_STATUS), each y.shape[1:]."""
+    lib = _abi.load()
+    if not torch.is_tensor(y) or not y.is_cuda or y.dtype != torch.float32 or y.dim() < 1:
+        raise ValueError("y must be a float32 device tensor [R, ...]")
+    if y.dim() == 2 and y.stride(1) == 1 and y.stride(0) >= y.shape[1]:
+        ld = y.stride(0)
+    else:
+        y = y.contiguous()
+        ld = int(np.prod(y.shape[1:], dtype=np.int64)) if y.dim() > 1 else 1
+    R, cols = y.shape[0], tuple(y.shape[1:])
+    C = int(np.prod(cols, dtype=np.int64)) if cols else 1
+    dev = y.device
+    if first is not None:
+        first = torch.as_tensor(first, device=dev).to(torch.int32).contiguous()
+        if first.numel() != C:
+            raise ValueError(f"first must hold one row index per column ({C})")
+    ml = -1 if maxlag is None else int(maxlag)
+    if ml < -1:
+        raise ValueError("maxlag must be None or >= 0")
+    nbytes = lib.pmenv_adf_workspace(R, C, ml)
+    if work is None:
+        work = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
+    if out is None:
+        out = {k: torch.empty(cols, dtype=torch.float64, device=dev) for k in ("stat", "pvalue")}
+        out.update({k: torch.empty(cols, dtype=torch.int32, device=dev) for k in ("usedlag", "nobs", "status")})
+    _abi.check(lib.pmenv_adf(_ptr(y), R, C, ld, _ptr(first) if first is not None else None, ml, int(bool(autolag)),
+                             _ptr(out["stat"]), _ptr(out["pvalue"]), _ptr(out["usedlag"]), _ptr(out["nobs"]),
+                             _ptr(out["status"]), _ptr(work), work.numel() * 8, _stream(dev)), None, "pmenv_adf")
+    return out
+
+
+D_TOL = 1e-5          # ffd.py:62,65: the bisection ends within 1e-5 of 0 or of the last probe
+D_ROUNDS = 16         # the k-th probe sits 2^-k from the one before: 2^-17 < 1e-5 ends the 17th round
+
+
+class _Search:
+    """The device state of find_d and one round of it (table -> apply -> adf -> update), every
+    buffer allocated up front: a round enqueues kernels only, so it can be captured."""
+
+    def __init__(self, x, thres, d_init=None, mask=None):
+        self.lib = _abi.load()
+        T, C = x.shape
+        dev = x.device
+        self.T, self.C, self.cap, self.thres, self.dev = T, C, T - 1, float(thres), dev
+        self.xpad = torch.zeros(self.cap + T, C, dtype=torch.float32, device=dev)   # row cap + r is series row r
+        self.xpad[self.cap:] = x
+        act = np.ones(C, dtype=bool) if mask is None else np.broadcast_to(np.asarray(mask, dtype=bool), (C,)).copy()
+        d0 = np.zeros(C) if d_init is None else np.broadcast_to(np.asarray(d_init, dtype=np.float64), (C,)).copy()
+        if not np.all(np.isfinite(d0)) or np.any(d0 < 0):
+            raise ValueError("d_init must be finite and >= 0")
+        act &= ~(d0 > 0)
+        f64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)  # noqa: E731
+        self.low, self.high, self.d_opt = f64(np.zeros(C)), f64(np.ones(C)), f64(np.where(d0 > 0, d0, 0.0))
+        self.active = torch.from_numpy(act.astype(np.int32)).to(dev)
+        self.evals = torch.zeros(C, dtype=torch.int32, device=dev)
+        self.status = torch.zeros(C, dtype=torch.int32, device=dev)
+        self.last = torch.full((2, C), float("nan"), dtype=torch.float64, device=dev)
+        self.d = torch.empty(C, dtype=torch.float64, device=dev)
+        self.taps = torch.empty(self.cap, C, dtype=torch.float32, device=dev)
+        self.width = torch.empty(C, dtype=torch.int32, device=dev)
+        self.first = torch.empty(C, dtype=torch.int32, device=dev)
+        self.y = torch.empty(T, C, dtype=torch.float32, device=dev)
+        self.res = {k: torch.empty(C, dtype=torch.float64, device=dev) for k in ("stat", "pvalue")}
+        self.res.update({k: torch.empty(C, dtype=torch.int32, device=dev) for k in ("usedlag", "nobs", "status")})
+        nbytes = self.lib.pmenv_adf_workspace(T, C, -1)
+        if nbytes == 0:
+            raise ValueError(f"a series of {T} rows is outside pmenv_adf's range (lag bound above 64)")
+        self.work = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+
+    def update(self, probed):
+        r = self.res
+        _abi.check(self.lib.pmenv_adf_search_update(
+            _ptr(r["pvalue"]) if probed else None, _ptr(r["stat"]) if probed else None,
+            _ptr(r["status"]) if probed else None, D_TOL, self.C, _ptr(self.low), _ptr(self.high),
+            _ptr(self.d_opt), _ptr(self.active), _ptr(self.evals), _ptr(self.status), _ptr(self.last), _ptr(self.d),
+            _stream(self.dev)), None, "pmenv_adf_search_update")
+
+    def table(self):
+        ffd_table(self.d, self.thres, self.T, self.cap, self.taps, self.width)
+
+    def round(self):
+        """One probe of every column at d: its taps, its own T - w + 1 outputs (the series is
+        padded in front by cap rows and filtered with max_width = cap, so output row r is series
+        row r and column c is valid from row w_c - 1), their ADF p-value, the bracket's update."""
+        self.table()
+        ffd_apply(self.xpad, self.taps, self.width, self.cap, out=self.y)
+        torch.sub(self.width, 1, out=self.first)
+        self.first.clamp_(min=0)
+        adf(self.y, first=self.first, out=self.res, work=self.work)
+        self.update(True)
+
+
+def find_d(x, thres=1e-5, d_init=None, mask=None):
+    """The orders of differencing of every column of x [T, ...] (device, f32): ffd.py:59-78,
+    FixedFracDiff.fit's bisection, for all columns at once on the device — per round the tap
+    table of every column's d_mid (pmenv_ffd_table), each column's own T - w + 1 FFD outputs
+    (pmenv_ffd_apply), their ADF p-values (pmenv_adf) and the bracket update
+    (pmenv_adf_search_update), with no host read before the end. thres is the taps' threshold
+    (ffd.py:43); the bisection's own tolerance is the reference's 1e-5. d_init (broadcastable to
+    x.shape[1:]): columns with a value > 0 keep it and are not searched; mask (bool, likewise):
+    columns it leaves out keep d = 0 (the reference's feat_ignore columns). Returns (d float64
+    numpy x.shape[1:], info): info holds pvalue and stat of each column's last probe (NaN if it
+    had none), width of its d, evals (probes taken) and status (of the last probe), numpy each."""
+    x = torch.as_tensor(x)
+    if not x.is_cuda:
+        x = x.to("cuda")
+    x = x.to(torch.float32).contiguous()
+    T, cols = x.shape[0], tuple(x.shape[1:])
+    if T < 3:
+        raise ValueError("x must have at least 3 rows")
+    C = int(np.prod(cols, dtype=np.int64)) if cols else 1
+    flat = lambda a: None if a is None else np.broadcast_to(np.asarray(a), cols).reshape(-1)  # noqa: E731
+    s = _Search(x.reshape(T, C), thres, flat(d_init), flat(mask))
+    s.update(False)
+    for _ in range(D_ROUNDS):
+        s.round()
+    s.table()                                   # the widths of the final d
+    d = s.d.cpu().numpy().reshape(cols)
+    last = s.last.cpu().numpy()
+    info = {"pvalue": last[0].reshape(cols), "stat": last[1].reshape(cols),
+            "width": s.width.cpu().numpy().reshape(cols), "evals": s.evals.cpu().numpy().reshape(cols),
+            "status": s.status.cpu().numpy().reshape(cols)}
+    return d, info
 
 
 def scale(x, method="minmax", stats=None, out=None):
@@ -270,10 +440,14 @@ _indicators = indicators      # build()'s `indicators` argument shadows the func
 
 
 def build(raw, d, thres=1e-5, train_ratio=0.8, scaler="minmax", close_channel=3, device=None, indicators=None,
-          channels=(0, 1, 2, 3, 4), channel_names=None):
+          channels=(0, 1, 2, 3, 4), channel_names=None, auto_channels=None):
     """The reference loader's order on the device. raw [T, N, C] (numpy or torch): C market
     channels per asset, raw prices in `close_channel`; d: a scalar, [C] or [N, C] orders of
-    differencing, 0 = leave the channel alone (the reference's feat_ignore columns);
+    differencing, 0 = leave the channel alone (the reference's feat_ignore columns), or "auto":
+    find_d searches them after steps 1 and 1b over the whole series (InstrumentPool.stationary
+    runs before the split) for the channels `auto_channels` names — by default the raw channels
+    except the volume channel (channels[4]), none of the indicators', as the reference's
+    feat_ignore list leaves volume and the oscillators alone; every other channel keeps d = 0;
     scaler "minmax", "standard" or None.
 
       1. relatives[t] = close[t+1] / close[t] and the features are rows 1: (instrument.py:79-80)
@@ -288,7 +462,8 @@ def build(raw, d, thres=1e-5, train_ratio=0.8, scaler="minmax", close_channel=3,
       4. each part scaled on its own, per (asset, channel) column (instrument.py:331-336)
 
     Returns (train, test): MarketSeries whose .relatives [T', N] row t belongs to bars[t],
-    with .widths (int32 [N, C]) and .max_width; with `indicators` also .channel_names (the raw
+    with .widths (int32 [N, C]), .max_width and .d (float64 numpy [N, C], the orders used:
+    given or found); with `indicators` also .channel_names (the raw
     channels' names, `channel_names` or "c0" .. , then the indicators') and
     .indicator_lookback.
 
@@ -319,6 +494,17 @@ def build(raw, d, thres=1e-5, train_ratio=0.8, scaler="minmax", close_channel=3,
             raise ValueError("channel_names must name the C raw channels")
         names = raw_names + ind_names
         feats, rel = both, rel[look:]
+    if isinstance(d, str):
+        if d != "auto":
+            raise ValueError('d must be numbers or "auto"')
+        if auto_channels is None:
+            auto_channels = [c for c in range(C) if c != channels[4]]
+        mask = np.zeros(feats.shape[2], dtype=bool)
+        mask[[int(c) for c in auto_channels]] = True
+        d, _ = find_d(feats, thres, mask=mask)
+    elif auto_channels is not None:
+        raise ValueError('auto_channels goes with d="auto"')
+    d = np.broadcast_to(np.asarray(d, dtype=np.float64), tuple(feats.shape[1:])).copy()
     x, widths, mw = frac_diff(feats, d, thres)                         # 2
     rel = rel[mw:]
     n = x.shape[0]
@@ -329,7 +515,7 @@ def build(raw, d, thres=1e-5, train_ratio=0.8, scaler="minmax", close_channel=3,
         if scaler is not None and bars.shape[0] > 0:                   # 4
             scale(bars, scaler, out=bars)
         s = MarketSeries(bars, device=dev, relatives=rel[lo:hi].contiguous())
-        s.widths, s.max_width = widths, mw
+        s.widths, s.max_width, s.d = widths, mw, d
         if names is not None:
             s.channel_names, s.indicator_lookback = names, look
         parts.append(s)
